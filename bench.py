@@ -6,14 +6,21 @@ activations already resident in HBM (one Hyena layer call: out = causal_conv(u, 
 du, dk, dbias for a random upstream gradient).  Default workload = the configuration BASELINE.json quotes the
 metric on: L = 1,048,576, d = 256, B = 1 per GPU, bf16 activations, fp32 filter (hyenadna-large-1m's layer).
 
-    python bench.py                      # 1 GPU, default K / W
+    python bench.py                      # 1 GPU, default K / W: the headline only
+    python bench.py --full               # ... and every secondary figure below
+    python bench.py --dump-outputs DIR   # ... and what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the two rooflines of
+the timed region (computed from its time, no run of their own).  Everything else -- `sweep`, `sweep_extra`,
+`sweep_real`, `operator_layer*`, `model_step*`, `real_shapes`, `cpu_baseline` and, for N > 1, `dist` -- is measured
+only with --full (null otherwise).
 
 Multi-GPU: the path shards on the batch axis (independent sequences): every rank runs the same
 per-GPU workload on its own seeded batch (weak scaling).  The convolution itself has no exchange step, so the timed
 region (`value`) carries no collective.  The only collective of the training step this path belongs to is DDP's gradient
-all-reduce, and that is measured where it lives: at every N the line also carries `model_step` -- the REAL
+all-reduce, and that is measured where it lives: with --full, at every N the line also carries `model_step` -- the REAL
 hyenadna model (hyena_dna_amd.lm.HyenaDNALM, north_star configuration 5: d_model 256, n_layer 8, d_inner 1024) on this
 rank's synthetic token batch, forward + backward + AdamW, for N > 1 wrapped in torch DistributedDataParallel exactly as
 the reference's trainer does (train.py:611-620: find_unused_parameters=False, gradient_as_bucket_view=True; RCCL carries
@@ -131,6 +138,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=1, help="sequences per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--chunk", type=int, default=0, help="channels per kernel-chain pass (0 = library default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures (sweeps, operator layer, model step, real shapes, cpu_baseline, N > 1 diagnostics); "
+                         "the --no-* options below select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (out; du, dk, dbias) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (a fixed sample of larger arrays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-model", action="store_true", help="skip the secondary full-model step (for N > 1: the DDP-wrapped model)")
     ap.add_argument("--model-layers", type=int, default=8, help="n_layer of the secondary full-model step (hyenadna-large-1m: 8)")
@@ -145,7 +158,10 @@ def parse():
     ap.add_argument("--emu", action="store_true",
                     help="TEST ONLY: run the host logic on the CPU emulation of the kernels with the gloo backend")
     ap.add_argument("--cpu-worker", default=None, help="INTERNAL: one pinned channel group of cpu_baseline (a JSON spec); no GPU is touched")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _cpu_once(u, k, bias, dout):
@@ -560,13 +576,15 @@ def make_conv_step(L, B, D, dtype, dev, seed, chunk=None, save=True, fwd_only=Fa
     dout = rows(torch.randn(B, D, L, generator=g, device=dev).to(dtype))
 
     def step():
+        """what a caller of the layer call receives: {"out"} (+ {"du", "dk", "dbias"} unless fwd_only)"""
         if save:
             out, saved = _lib.fftconv_fwd(u, k, bias, chunk=chunk, save=True)
         else:
             out, saved = _lib.fftconv_fwd(u, k, bias, chunk=chunk), None
         if fwd_only:
-            return out
-        return _lib.fftconv_bwd(dout, u, k, bias, chunk=chunk, saved=saved)
+            return {"out": out}
+        du, dk, dbias = _lib.fftconv_bwd(dout, u, k, bias, chunk=chunk, saved=saved)
+        return {"out": out, "du": du, "dk": dk, "dbias": dbias}
 
     return step
 
@@ -574,9 +592,11 @@ def make_conv_step(L, B, D, dtype, dev, seed, chunk=None, save=True, fwd_only=Fa
 def maybe_graph(step, L, B, D, dtype, dev, warmup, enabled):
     """Launch-bound sizes (a hyenadna-tiny-1k layer call is ~15 us of GPU work behind ~35 us of Python + ctypes per call): the step is
     captured into ONE hipGraph and replayed -- the same launches on the same buffers, issued by the runtime instead of the interpreter
-    (what lm.GraphedTrainStep does for the whole training step)."""
+    (what lm.GraphedTrainStep does for the whole training step).
+    Returns (run, graphed, captured): captured = the graph's own output tensors, which every replay overwrites (None when not graphed:
+    then run() returns the outputs itself)."""
     if not enabled or algorithmic_bytes(B, D, L, 2 if dtype != torch.float32 else 4) > 64 * 2 ** 20:
-        return step, False
+        return step, False, None
     side = torch.cuda.Stream(dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
@@ -585,11 +605,38 @@ def maybe_graph(step, L, B, D, dtype, dev, warmup, enabled):
         side.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=side):
-            step()
+            captured = step()
     torch.cuda.current_stream(dev).wait_stream(side)
     for _ in range(warmup):
         graph.replay()
-    return graph.replay, True
+    return graph.replay, True, captured
+
+
+DUMP_BYTES = 64_000_000       # --dump-outputs: all files together, headers included
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every tensor of `outputs` ({name: tensor}) as out_dir/<name>.npy in float32.  An array larger than its even share of
+    DUMP_BYTES is sampled: n of its elements in row-major order of its logical shape, one from each of n equal strides at a seeded offset --
+    the same positions in every run with the same arguments, so two builds can be compared element for element.  Returns {name: sampled?}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BYTES - 4096 * len(outputs)) // max(1, len(outputs)) // 4
+    sampled = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        n = t.numel()
+        if n <= share:
+            a = t.float().cpu().numpy()
+        else:
+            stride = n // share
+            g = torch.Generator().manual_seed(2222)
+            flat = torch.arange(share, dtype=torch.int64) * stride + torch.randint(0, stride, (share,), generator=g)
+            idx = torch.unravel_index(flat.to(t.device), t.shape)      # rows may be pitched: index the logical shape, not the storage
+            a = t[idx].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        sampled[name] = n > share
+    return sampled
 
 
 def conv_rooflines(L, B, D, dtype_name, save, ev_ms_step):
@@ -642,7 +689,7 @@ def sweep_configs(dtype, dtype_name, dev, steps, warmup, graph_ok, emu=False, co
             step = make_conv_step(L, B, D, dtype, dev, seed=2222, pitched=pitched)
             for _ in range(warmup):
                 step()
-            run, graphed = (step, False) if emu else maybe_graph(step, L, B, D, dtype, dev, warmup, graph_ok)
+            run, graphed = (step, False) if emu else maybe_graph(step, L, B, D, dtype, dev, warmup, graph_ok)[:2]
             if emu:
                 t0 = time.perf_counter()
                 for _ in range(steps):
@@ -889,14 +936,15 @@ def main():
         step()
     sync()
     # --no-graph times the eager calls at the launch-bound sizes too
-    run_step, graphed = (step, False) if args.emu else maybe_graph(step, L, B, D, dtype, dev, args.warmup, not args.no_graph)
+    run_step, graphed, captured = (step, False, None) if args.emu else maybe_graph(step, L, B, D, dtype, dev, args.warmup, not args.no_graph)
     sync()
     if not args.emu:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         run_step()
+    last = run_step()                      # (kept for --dump-outputs; a graph replay returns nothing: its outputs are `captured`)
     if not args.emu:
         e1.record()
     sync()
@@ -907,16 +955,21 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     wall = tmax.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(captured if graphed else last, args.dump_outputs)
+    last = None
 
+    # everything below is a secondary figure: --full only
+    full = args.full
     dist_info = None
-    if world > 1:
+    if full and world > 1:
         try:
             dist_info = dist_diagnostics(dev, rank, world, wall * 1e3 / args.steps, local_wall * 1e3 / args.steps, args, nccl_log)
         except Exception as e:                                       # diagnostics never cost the contract line
             dist_info = {"error": repr(e)[:300]}
 
     sweep = sweep_extra = None
-    if world == 1 and not args.no_sweep and not args.fwd_only:
+    if full and world == 1 and not args.no_sweep and not args.fwd_only:
         # the four other contract configurations, same loop (rank 0 of an N = 1 run only: a sweep is not part of the scaling legs)
         sweep = sweep_configs(dtype, args.dtype, dev, max(args.steps, 20) if not args.emu else 1, args.warmup if not args.emu else 0,
                               not args.no_graph, emu=args.emu, configs=[(256, 2, 64)] if args.emu else None)
@@ -924,11 +977,11 @@ def main():
             sweep_extra = sweep_configs(dtype, args.dtype, dev, max(args.steps, 20), args.warmup, not args.no_graph, configs=SWEEP_EXTRA)
 
     sweep_real = None
-    if world == 1 and not args.no_sweep and not args.fwd_only and not args.emu:
+    if full and world == 1 and not args.no_sweep and not args.fwd_only and not args.emu:
         sweep_real = sweep_real_shapes(dtype, args.dtype, dev, max(args.steps, 20), args.warmup, not args.no_graph)
 
     model_res = None
-    if not args.no_model and not args.fwd_only and (world > 1 or not args.emu):
+    if full and not args.no_model and not args.fwd_only and (world > 1 or not args.emu):
         # every rank takes part (DDP's collectives); a failure must not lose the contract line, nor leave the other ranks
         # inside a collective: the exception is reported and every rank then moves on to the final barrier
         try:
@@ -956,17 +1009,17 @@ def main():
                                       if world > 1 else "single GPU",
                        "unit_of_work": "one nucleotide through one Hyena long-conv layer call (fwd+bwd), all d channels"},
             # N > 1: what lets a reader of SCALE_r*.json see that N ranks really met over RCCL (backend, library version, devices, every rank's own
-            # step time, one timed 26 MB gradient-sized all_reduce outside the timed region, RCCL's transport lines); null at N = 1
+            # step time, one timed 26 MB gradient-sized all_reduce outside the timed region, RCCL's transport lines); --full only, null at N = 1
             "dist": dist_info,
             "roofline": roof,
             "roofline_valu": valu,
-            # the other four BASELINE.json configurations through the same loop (N = 1 runs; null otherwise)
+            # the other four BASELINE.json configurations through the same loop (N = 1 runs with --full; null otherwise)
             "sweep": sweep,
             "sweep_extra": sweep_extra,
             # the lengths the reference's trainer really produces (L = max_length - 1), each next to its aligned neighbour
             "sweep_real": sweep_real,
         }
-        if world == 1 and not args.emu and not args.no_operator and not args.fwd_only:
+        if full and world == 1 and not args.emu and not args.no_operator and not args.fwd_only:
             try:
                 line["operator_layer"] = operator_layer(L, D, B, dtype, dev)
             except Exception as e:                                   # secondary: never lose the contract line over it
@@ -988,7 +1041,7 @@ def main():
             except Exception as e:
                 line["operator_layer_order3"] = {"error": repr(e)[:200]}
         line["model_step"] = model_res
-        if world == 1 and not args.emu and not args.no_sweep and not args.fwd_only and L % 2 == 0:
+        if full and world == 1 and not args.emu and not args.no_sweep and not args.fwd_only and L % 2 == 0:
             # the layer and the model at the length the reference's trainer feeds them for this max_length: L - 1
             if not args.no_operator:
                 try:
@@ -1008,13 +1061,13 @@ def main():
                     line["model_step_real"] = r
                 except Exception as e:
                     line["model_step_real"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.emu and not args.no_sweep and not args.fwd_only and not (args.no_operator and args.no_model):
+        if full and world == 1 and not args.emu and not args.no_sweep and not args.fwd_only and not (args.no_operator and args.no_model):
             # the shipped experiments' own (B, L, d_model, n_layer) at the operator and the model level, next to their aligned neighbours
             try:
                 line["real_shapes"] = real_shape_legs(dtype, dev, no_operator=args.no_operator, no_model=args.no_model)
             except Exception as e:
                 line["real_shapes"] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline and not args.emu:
+        if full and world == 1 and not args.no_cpu_baseline and not args.emu:
             line["cpu_baseline"] = cpu_baseline(L, D, dtype)          # rank 0 at N = 1 only (other ranks would idle at the barrier)
         else:
             line["cpu_baseline"] = None

@@ -9,11 +9,11 @@ cd $R
 export TMPDIR=/tmp
 echo "== smoke"; timeout 600 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -3 $OUT/smoke.log
 echo "== pytest -m gpu"; timeout 900 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -5 $OUT/pytest_gpu.log
-echo "== bench L=1M"; timeout 600 python bench.py > $OUT/bench_1m.json 2> $OUT/bench_1m.err; echo "bench rc=$?"; cat $OUT/bench_1m.json
+echo "== bench L=1M"; timeout 600 python bench.py --full > $OUT/bench_1m.json 2> $OUT/bench_1m.err; echo "bench rc=$?"; cat $OUT/bench_1m.json
 for cfg in "1024 128 8" "32768 256 8" "160000 256 2" "450560 256 1"; do
   set -- $cfg
   echo "== bench L=$1 d=$2 B=$3"
-  timeout 300 python bench.py --seq-len $1 --d-model $2 --batch $3 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_L$1.json 2> $OUT/bench_L$1.err
+  timeout 300 python bench.py --full --seq-len $1 --d-model $2 --batch $3 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_L$1.json 2> $OUT/bench_L$1.err
   cat $OUT/bench_L$1.json
 done
 echo "== bench L=1M fwd only / chunk sweep"
@@ -22,7 +22,7 @@ for c in 2 4 8 16 32; do
 done
 echo "== rocprofv3 kernel stats"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench1m -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench1m -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1
 echo "rocprof rc=$?"
 find $OUT/prof -name '*kernel_stats*' | head -3
 f=$(find $OUT/prof -name '*kernel_stats*.csv' | head -1); [ -n "$f" ] && head -20 "$f"

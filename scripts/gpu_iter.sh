@@ -18,6 +18,6 @@ for cfg in "32768 256 8" "160000 256 2"; do
 done
 echo "== rocprofv3 kernel stats (L=1M, default chunk)"
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench1m -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench1m -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/rocprof.log 2>&1
 echo "rocprof rc=$?"
 python $R/scripts/rocpd_stats.py $(find $OUT/prof -name '*.db' | head -1) $OUT/kernel_stats.csv | grep hyena | cut -c1-150

@@ -13,7 +13,7 @@ def _run(nproc, port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--steps", "2", "--warmup", "1", "--emu", "--seq-len", "3000", "--d-model", "4",
-           "--batch", "1", "--dtype", "bf16", "--model-layers", "2"]
+           "--batch", "1", "--dtype", "bf16", "--model-layers", "2", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -65,7 +65,7 @@ def test_rccl_log_summary_counts_transports(tmp_path):
 def test_bench_single_process_line_shape():
     env = dict(os.environ, OMP_NUM_THREADS="2")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--steps", "1", "--warmup", "0",
-                        "--seq-len", "1024", "--d-model", "2"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--seq-len", "1024", "--d-model", "2", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -85,6 +85,75 @@ def test_bench_single_process_line_shape():
             assert key in c, key
         assert c["unit"] == "nt/s" and c["ms_per_step"] > 0
         assert abs(c["value"] - c["batch_per_gpu"] * c["seq_len"] / (c["ms_per_step"] * 1e-3)) / c["value"] < 1e-6
+
+
+def _plain(tmp_path, *extra):
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emu", "--steps", "3", "--warmup", "1",
+                        "--seq-len", "1024", "--d-model", "2", "--batch", "2", *extra], cwd=str(tmp_path), env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """without --full the line carries the timed region's figures and nothing that takes a run of its own"""
+    r = _plain(tmp_path)
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["unit"] == "nt/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["metric"].startswith("nucleotides/sec")
+    assert abs(r["value"] - 2 * 1024 / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+    assert r["roofline"]["bound"] == "hbm" and r["roofline_valu"]["bound"] == "valu_fp32"
+    for key in ("sweep", "sweep_extra", "sweep_real", "model_step", "cpu_baseline", "dist"):
+        assert r[key] is None, key
+    for key in ("operator_layer", "operator_layer_order3", "operator_layer_real", "model_step_real", "real_shapes"):
+        assert key not in r, key
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the last timed step's out, du, dk, dbias as float32 .npy files, the same in every run with the same arguments"""
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = _plain(tmp_path, "--dump-outputs", str(d))
+        assert r["steps"] == 3
+        files = sorted(os.listdir(d))
+        assert files == ["dbias.npy", "dk.npy", "du.npy", "out.npy"], files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert arrs["out"].shape == arrs["du"].shape == (2, 2, 1024) and arrs["dk"].shape == (2, 1024) and arrs["dbias"].shape == (2,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert np.abs(arrs["out"]).max() > 0 and np.abs(arrs["dk"]).max() > 0
+        got.append(arrs)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """an array above its share of the 64 MB budget is written as a fixed sample: the same positions every time, within the budget"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * (4096 + 4 * 1000))       # a share of 1000 elements per array
+    big = torch_arange_rows()
+    small = big[0, 0, :10].clone()
+    assert bench.dump_outputs({"big": big, "small": small}, str(tmp_path / "a")) == {"big": True, "small": False}
+    bench.dump_outputs({"big": big, "small": small}, str(tmp_path / "b"))
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.shape == (1000,) and a.dtype == np.float32 and np.array_equal(a, b)
+    # the sample holds values of the logical (strided) tensor, in row-major order, one from each stride
+    assert np.all(np.diff(a) > 0) and a.min() >= 0 and a.max() < big.numel()
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.arange(10, dtype=np.float32))
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= bench.DUMP_BYTES
+
+
+def torch_arange_rows():
+    """(2, 3, 5000) float tensor holding its own row-major index, laid out on pitched rows (a view of wider rows)"""
+    import torch
+    base = torch.zeros(2, 3, 5120)
+    base[..., :5000] = torch.arange(2 * 3 * 5000, dtype=torch.float32).reshape(2, 3, 5000)
+    return base[..., :5000]
 
 
 def test_bench_sweep_names_the_four_other_contract_configurations():
