@@ -167,6 +167,16 @@ def lib():
         L.hyena_cm_pre_bwd_ld.restype = c_int
         L.hyena_cm_pre_bwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int, c_int, c_int, c_int, ctypes.c_long, c_int, c_int, c_int, c_void_p]
+        # one-position decode step (include/hyena_decode.h)
+        L.hyena_decode_partial_floats.restype = c_size_t
+        L.hyena_decode_partial_floats.argtypes = [c_int, c_int, c_int]
+        L.hyena_decode_pre.restype = c_int
+        L.hyena_decode_pre.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+        L.hyena_decode_conv.restype = c_int
+        L.hyena_decode_conv.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+        L.hyena_decode_post.restype = c_int
+        L.hyena_decode_post.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -728,6 +738,48 @@ def cm_pre_bwd(dvg, xT, bin_, w, b, dxT, part):
         check(lib().hyena_cm_pre_bwd_ld(dvg.data_ptr(), xT.data_ptr(), None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
                                         dxT.data_ptr(), part.data_ptr(), B, L, xT.shape[2], D, csx, bsx, ld_of(dvg), dtype_code(xT.dtype),
                                         _backend.stream(xT.device)))
+
+
+# ---- one decode position (include/hyena_decode.h): hist is the (Bcap, D, lda) history of the convolution's input, pos a one-int device tensor ----
+def decode_partials(B, D, Lcap, device):
+    return torch.empty(lib().hyena_decode_partial_floats(int(B), int(D), int(Lcap)), dtype=torch.float32, device=device)
+
+
+def _hist(hist):
+    assert hist.dim() == 3 and hist.stride(2) == 1 and hist.stride(1) * hist.shape[1] == hist.stride(0)
+    return hist.shape[0], hist.shape[1], hist.stride(1)
+
+
+def decode_pre(x2, bin_, w, b, tail, hist, x0, pos, Lcap):
+    """x2 (B, 3D) in_proj output of the new position without bias (rows contiguous) -> hist[:, :, t] = v * x1, x0 (B, D) fp32, tail shifted"""
+    _require_gpu(x2, "x")
+    B, D3 = x2.shape
+    Bcap, D, lda = _hist(hist)
+    assert D3 == 3 * D and x2.stride(1) == 1 and hist.dtype == x2.dtype
+    with _backend.guard(x2.device):
+        check(lib().hyena_decode_pre(x2.data_ptr(), x2.stride(0), None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                     tail.data_ptr(), hist.data_ptr(), x0.data_ptr(), pos.data_ptr(), B, Bcap, D, int(Lcap), lda,
+                                     dtype_code(x2.dtype), _backend.stream(x2.device)))
+
+
+def decode_conv(k, hist, part, pos, B, Lcap):
+    """part[chunk][b][d] = the chunk's share of sum_{s <= t} k[d, t - s] hist[b, d, s]; k (D, ldk) fp32 rows contiguous"""
+    _require_gpu(k, "k")
+    _, D, lda = _hist(hist)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv(k.data_ptr(), k.stride(0), hist.data_ptr(), part.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap), lda,
+                                      dtype_code(hist.dtype), _backend.stream(k.device)))
+
+
+def decode_post(part, hist, fb, x0, z, pos, B, Lcap):
+    """z (B, D) = round(round(sum of the partials + fb hist[:, :, t]) * x0); advances pos"""
+    _require_gpu(z, "z")
+    _, D, lda = _hist(hist)
+    assert z.dtype == hist.dtype and z.is_contiguous()
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(), z.data_ptr(),
+                                      pos.data_ptr(), int(B), D, int(Lcap), lda, dtype_code(hist.dtype), _backend.stream(z.device)))
 
 
 # ---- input projection on the matrix cores with the front of the shell in its epilogue (include/hyena_proj.h) --------------------

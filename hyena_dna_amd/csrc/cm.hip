@@ -1,8 +1,11 @@
-// cm.hip -- host side of the channel-major operator shell (cm_kernels.h; C ABI in include/hyena_mixer.h).
+// cm.hip -- host side of the channel-major operator shell (cm_kernels.h; C ABI in include/hyena_mixer.h) and of its one-position decode
+// step (decode_kernels.h; C ABI in include/hyena_decode.h).
 #include "cm_kernels.h"
+#include "decode_kernels.h"
 #include "launch.h"
 #include "../../include/hyena_fftconv.h"
 #include "../../include/hyena_mixer.h"
+#include "../../include/hyena_decode.h"
 
 using namespace hyena;
 
@@ -107,6 +110,78 @@ int hyena_cm_post_bwd(const void* dzT, const void* y, const void* xT, const floa
 int hyena_cm_pre_bwd(const void* dvg, const void* xT, const float* bin, const float* w, const float* b, void* dxT, float* part, int B,
                      int L, int Lx, int D, int dtype, void* stream) {
     return hyena_cm_pre_bwd_ld(dvg, xT, bin, w, b, dxT, part, B, L, Lx, D, (long)B * Lx, Lx, L, dtype, stream);
+}
+
+}  // extern "C"
+
+// ---- the one-position decode step (decode_kernels.h) ----------------------------------------------------------------------------------
+namespace {
+const int DEC_MAX_L = 1 << 20;
+bool dec_dtype_ok(int dtype) { return dtype == HYENA_F32 || dtype == HYENA_BF16 || dtype == HYENA_F16; }
+bool dec_aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
+// the history rows: lda >= Lcap, 8-element multiple (every 8-element vector of a row is one aligned 16 / 32-byte access and never crosses its end)
+bool dec_hist_ok(const void* vg, int B, int D, int Lcap, int lda, int dtype) {
+    return vg != nullptr && dec_aligned16(vg) && B >= 1 && D >= 1 && Lcap >= 1 && Lcap <= DEC_MAX_L && lda >= Lcap && lda % DEC_V == 0 &&
+           dec_dtype_ok(dtype);
+}
+int dec_chunks(int Lcap) { return (Lcap + DEC_CHUNK - 1) / DEC_CHUNK; }
+DecArgs dec_args() {
+    DecArgs a;
+    a.x = nullptr; a.bin = nullptr; a.w = nullptr; a.b = nullptr; a.tail = nullptr; a.vg = nullptr; a.x0 = nullptr; a.k = nullptr;
+    a.part = nullptr; a.fb = nullptr; a.z = nullptr; a.pos = nullptr;
+    a.B = a.D = a.Bcap = a.Lcap = a.ldx = a.lda = a.ldk = 0;
+    return a;
+}
+#define HY_DEC_DISPATCH(kernel, grid, threads, smem)                                                                  \
+    do {                                                                                                              \
+        switch (dtype) {                                                                                              \
+            case HYENA_F32: HY_LAUNCH((kernel<DT_F32>), grid, dim3(threads), smem, stream, a); break;                 \
+            case HYENA_BF16: HY_LAUNCH((kernel<DT_BF16>), grid, dim3(threads), smem, stream, a); break;               \
+            default: HY_LAUNCH((kernel<DT_F16>), grid, dim3(threads), smem, stream, a); break;                        \
+        }                                                                                                             \
+    } while (0)
+}  // namespace
+
+extern "C" {
+
+size_t hyena_decode_partial_floats(int B, int D, int Lcap) {
+    if (B < 1 || D < 1 || Lcap < 1 || Lcap > DEC_MAX_L) return 0;
+    return (size_t)dec_chunks(Lcap) * B * D;
+}
+
+int hyena_decode_pre(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vg, float* x0, const int* pos,
+                     int B, int Bcap, int D, int Lcap, int lda, int dtype, void* stream) {
+    if (x == nullptr || w == nullptr || b == nullptr || tail == nullptr || x0 == nullptr || pos == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) ||
+        Bcap < B || ldx < 3 * D || (long)Bcap * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.x = x; a.bin = bin; a.w = w; a.b = b; a.tail = tail; a.vg = vg; a.x0 = x0; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Bcap = Bcap; a.Lcap = Lcap; a.ldx = ldx; a.lda = lda;
+    HY_DEC_DISPATCH(decode_pre_kernel, dim3((B * D + DEC_THREADS - 1) / DEC_THREADS), DEC_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_conv(const float* k, int ldk, const void* vg, float* part, const int* pos, int B, int D, int Lcap, int lda, int dtype,
+                      void* stream) {
+    if (k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || pos == nullptr ||
+        !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || D > 65535)
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.k = k; a.vg = const_cast<void*>(vg); a.part = part; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_conv_kernel, dim3(dec_chunks(Lcap), D), DEC_THREADS, (DEC_KLDS + 8) * sizeof(float));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_post(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap, int lda,
+                      int dtype, void* stream) {
+    if (part == nullptr || x0 == nullptr || z == nullptr || pos == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || (long)B * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.part = const_cast<float*>(part); a.vg = const_cast<void*>(vg); a.fb = fb; a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda;
+    HY_DEC_DISPATCH(decode_post_kernel, dim3(1), DEC_POST_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,156 @@
+// decode_kernels.h -- one decode position of the order-2 Hyena operator for all B sequences (incremental generation).
+//
+// Every operation of the operator is per-position or causal, and the implicit filter is prefix-consistent (column j of filter_dl(L) does not
+// depend on L), so position t of the long convolution is a plain dot product over the history of its input:
+//     y_t[b, c] = sum_{s <= t} k[c, t - s] vg[b, c, s] + fb[c] vg[b, c, t]          vg = v * x1, the convolution's input (cm_kernels.h)
+// Three kernels per layer and position, between the in_proj and out_proj GEMVs (C ABI: include/hyena_decode.h):
+//   decode_pre   xT_t (+ b_in) and the two previous positions (tail state) -> the three short-conv outputs with cm_sc's FMA order, vg_t into
+//                column t of the history, the gate x0_t (fp32), the tail shifted by one
+//   decode_conv  sum_{s <= t} k[c, t - s] vg[b, c, s] in fp32 over a FIXED grid of (channel, history chunk) workgroups: one partial per
+//                (chunk, b, c), no atomics; chunks that start past t leave at once.  The grid depends on Lcap only, never on t.
+//   decode_post  the partials summed in chunk order, + fb vg_t, rounded to the I/O type where the forward rounds the convolution's output,
+//                times x0_t with cm_post_fwd's arithmetic -> z_t; then the position advances
+// The position t lives in device memory and all three kernels read it there: one captured graph serves every position.
+//
+// The two streams of decode_conv run in opposite directions (vg forward in s, k backward), and the k stream is misaligned by t mod 4 words
+// relative to the vg stream.  The history is the operand that scales with B, so ITS loads stay aligned 16-byte vectors (8 elements per lane at
+// 8-aligned positions of 8-aligned rows); the filter segment a workgroup needs, k[c, t - s0 - CHUNK + 1 .. t - s0], is staged ONCE into LDS with
+// aligned 16-byte loads (the segment rounded outwards to 4 words) and read back from LDS at the shifted, reversed index for every one of the B
+// rows: k's global bytes do not scale with B and no global load is under-aligned.  (Storing k reversed at cache-build time would put both
+// streams in one direction but leave the t mod 4 offset, i.e. under-aligned 16-byte k loads, and k re-read per row or B accumulators per lane.)
+#pragma once
+#include "cm_kernels.h"
+
+namespace hyena {
+
+enum { DEC_THREADS = 256, DEC_V = 8, DEC_NV = 4, DEC_CHUNK = DEC_THREADS * DEC_V * DEC_NV /* 8192 positions */, DEC_POST_THREADS = 1024,
+       DEC_KLDS = DEC_CHUNK + 8 /* floats of staged filter */ };
+
+struct DecArgs {
+    const void* x;      // pre: in_proj output of the new position without its bias, element (c, b) at b ldx + c, I/O type
+    const float* bin;   // (3D,) in_proj bias or null
+    const float* w;     // (3D, 3) short-filter taps
+    const float* b;     // (3D,) short-filter bias
+    float* tail;        // (3D, Bcap, 2) fp32: raw xT of positions t - 2, t - 1
+    void* vg;           // history (Bcap, D, lda) I/O type: row (b, d) at (b D + d) lda
+    float* x0;          // (B, D) fp32 gate of position t
+    const float* k;     // (D, ldk) fp32 filter, column j = tap j
+    float* part;        // [nchunks][B][D] fp32 partial sums
+    const float* fb;    // (D,) fp32 filter bias or null
+    void* z;            // (B, D) I/O type
+    int* pos;           // the position t (device memory)
+    int B, D, Bcap, Lcap, ldx, lda, ldk;
+};
+
+__device__ __forceinline__ float dec_sc(float xm2, float xm1, float xn, int t, float w0, float w1, float w2, float bsc, float bin) {
+    // cm_sc (cm_kernels.h) at one position: taps before position 0 are zero padding, explicit FMAs in the same order
+    const float x0 = t >= 2 ? xm2 + bin : 0.f, x1 = t >= 1 ? xm1 + bin : 0.f, x2 = xn + bin;
+    return __builtin_fmaf(w2, x2, __builtin_fmaf(w1, x1, __builtin_fmaf(w0, x0, bsc)));
+}
+
+// one thread per (b, d): grid ceil(B D / DEC_THREADS)
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_pre_kernel(DecArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int i = (int)(blockIdx.x * DEC_THREADS + threadIdx.x);
+    const int t = a.pos[0];
+    if (i >= a.B * a.D || t < 0 || t >= a.Lcap) return;
+    const int b = i / a.D, d = i % a.D;
+    const elem_t* x = reinterpret_cast<const elem_t*>(a.x);
+    float o[3];
+    HY_UNROLL
+    for (int g = 0; g < 3; ++g) {
+        const int c = g * a.D + d;
+        float* tl = a.tail + ((size_t)c * a.Bcap + b) * 2;
+        const float xm2 = tl[0], xm1 = tl[1];
+        const float xn = Elem<DT>::dec(x[(size_t)b * a.ldx + c]);
+        o[g] = dec_sc(xm2, xm1, xn, t, a.w[c * 3], a.w[c * 3 + 1], a.w[c * 3 + 2], a.b[c], a.bin != nullptr ? a.bin[c] : 0.f);
+        tl[0] = xm1;
+        tl[1] = xn;
+    }
+    elem_t* vg = reinterpret_cast<elem_t*>(a.vg);
+    vg[((size_t)b * a.D + d) * a.lda + t] = Elem<DT>::cvt(o[1] * o[2]);      // cm_pre_fwd: c1 * cv, rounded once
+    a.x0[(size_t)b * a.D + d] = o[0];
+}
+
+// grid (nchunks, D): workgroup (chunk, c) covers history positions [chunk DEC_CHUNK, (chunk + 1) DEC_CHUNK) of channel c for every b
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_conv_kernel(DecArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS;                                   // [2][4]: wavefront sums, alternating by row parity
+    const int t = a.pos[0];
+    const int chunk = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int s0 = chunk * DEC_CHUNK;
+    if (t < 0 || t >= a.Lcap || s0 > t) return;
+    // stage k[c, base .. t - s0] (base = t - s0 - DEC_CHUNK + 1 rounded down to 4 words; negative taps are zeros) with aligned 16-byte loads
+    const int jlo = t - s0 - DEC_CHUNK + 1;
+    const int base = jlo >= 0 ? (jlo & ~3) : -((3 - jlo) & ~3);
+    const int ngroups = (t - s0 - base) / 4 + 1;
+    const float* krow = a.k + (size_t)c * a.ldk;
+    for (int q = tid; q < ngroups; q += DEC_THREADS) {
+        const int j = base + 4 * q;
+        float r[4] = {0.f, 0.f, 0.f, 0.f};
+        if (j >= 0) __builtin_memcpy(r, krow + j, sizeof(r));
+        HY_UNROLL
+        for (int e = 0; e < 4; ++e) ks[4 * q + e] = r[e];
+    }
+    __syncthreads();
+    for (int b = 0; b < a.B; ++b) {
+        const char* row = cm_row(a.vg, (size_t)b * a.D + c, a.lda, ES);
+        float acc = 0.f;
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            if (s <= t) {                                                 // (s + DEC_V <= lda: rows are 8-aligned and t < Lcap <= lda)
+                // 16-byte aligned (rows start 16-byte aligned, lda and s are multiples of 8): one / two dwordx4 loads, also for fp32
+                // (positions past t inside the last vector are read and multiplied by a zero tap: the history holds finite values only --
+                // zeros from the cache's allocation or earlier steps' outputs; selecting the tap instead of the product keeps the load whole)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)s * ES, 16), sizeof(raw));
+                float x[DEC_V];
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) x[e] = Elem<DT>::dec(raw[e]);
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) {
+                    const bool ok = s + e <= t;
+                    const float kv = ks[ok ? t - s - e - base : 0];
+                    const float kk = ok ? kv : 0.f;
+                    acc = __builtin_fmaf(kk, x[e], acc);
+                }
+            }
+        }
+        acc = cm_wave_sum(acc);
+        HY_LDS float* rb = red + 4 * (b & 1);
+        if ((tid & 63) == 0) rb[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) a.part[((size_t)chunk * a.B + b) * a.D + c] = (rb[0] + rb[1]) + (rb[2] + rb[3]);
+    }
+}
+
+// ONE workgroup: every thread reads t before the barrier, one lane advances it after
+template <int DT>
+__global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_kernel(DecArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int t = a.pos[0];
+    const bool valid = t >= 0 && t < a.Lcap;
+    if (valid) {
+        const int nc = t / DEC_CHUNK + 1;
+        const elem_t* vg = reinterpret_cast<const elem_t*>(a.vg);
+        elem_t* z = reinterpret_cast<elem_t*>(a.z);
+        for (int i = threadIdx.x; i < a.B * a.D; i += DEC_POST_THREADS) {
+            const int b = i / a.D, d = i % a.D;
+            float y = 0.f;
+            for (int ch = 0; ch < nc; ++ch) y += a.part[((size_t)ch * a.B + b) * a.D + d];
+            const float u = Elem<DT>::dec(vg[((size_t)b * a.D + d) * a.lda + t]);
+            if (a.fb != nullptr) y = __builtin_fmaf(u, a.fb[d], y);
+            const float yr = Elem<DT>::dec(Elem<DT>::cvt(y));                 // the forward's convolution output is stored in the I/O type
+            z[i] = Elem<DT>::cvt(yr * a.x0[i]);                                // cm_post_fwd: y * c0, rounded once
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && valid) a.pos[0] = t + 1;
+}
+
+}  // namespace hyena

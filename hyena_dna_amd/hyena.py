@@ -347,6 +347,7 @@ class HyenaOperator(nn.Module):
         self.outer_mixing = outer_mixing
         self.activation = nn.Identity()
         self.return_state = return_state
+        self.layer_idx = filter_args.get("layer_idx")          # (the key of this layer's decode cache; still tolerated by the filter, as before)
         self.dropout = nn.Dropout(dropout)
 
         # projections (hyena.py:345-357)
@@ -411,29 +412,90 @@ class HyenaOperator(nn.Module):
         return hyena_mixer_out_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter, vg,
                                   self.out_proj.weight, self.out_proj.bias, add_norm=(residual, norm_weight, norm_bias, eps))
 
-    def forward(self, u, *args, **kwargs):
+    def _forward_fused_cm(self, u, l_filter, keep_vg=False):
+        """the fused channel-major route -> (y, xT, vg).  keep_vg: vg is made here (cm_pre_fwd on xT, what the mixer would run itself) when
+        the projection kernel does not hand it back -- the same kernel on the same operands, so y does not change by a bit."""
+        fside = _FilterOnSideStream(u, l_filter)
+        k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))           # (D, l), rows contiguous along l; on the second stream, next to in_proj
+        fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
+        # x^T = W_in u^T straight out of the GEMM (3D, B, L): nothing between the projections is ever transposed
+        # (16-bit operands at d_model 128 / 256: this package's MFMA kernel, which also hands back the conv's input v * x1
+        # from its epilogue -- csrc/proj_kernels.h; otherwise the library GEMM and vg = None)
+        xT, vg = in_proj_pre_cm(u, self.in_proj.weight, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias,
+                                l_filter)
+        fside.join(k)
+        if keep_vg and vg is None:
+            from . import _lib
+            D3 = xT.shape[0]
+            vg = _lib.cm_pre_fwd(_lib.as_cm(xT), self.in_proj.bias.detach().to(torch.float32).contiguous(),
+                                 self.short_filter.weight.detach().to(torch.float32).reshape(D3, 3).contiguous(),
+                                 self.short_filter.bias.detach().to(torch.float32).contiguous(), l_filter)
+        if l_filter > 0 and xT.shape[1] > 0 and mixer_out_supported(xT, l_filter, self.out_proj.weight):
+            # out_proj as this package's matrix-core kernel, the `* x0` gate on its operand load (csrc/proj_kernels.h, round 4)
+            y = hyena_mixer_out_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
+                                   vg, self.out_proj.weight, self.out_proj.bias)
+        else:
+            zT = hyena_mixer_core_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
+                                     vg=vg)
+            y = out_proj_cm(zT, self.out_proj.weight, self.out_proj.bias)   # activation is the identity (_fused_ok)
+        return y, xT, vg
+
+    # ---- incremental decoding (hyena_dna_amd/inference.py, csrc/decode_kernels.h) ----------------------------------------------------------------
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        """A ``HyenaDecodeState`` for up to batch_size sequences of up to max_seqlen positions, to be put into
+        ``InferenceParams.key_value_memory_dict`` under this operator's ``layer_idx`` (or the operator itself when it has none).  The cache is a
+        snapshot of the weights at this call, as a key-value cache is: build a new one after the weights change."""
+        from .inference import HyenaDecodeState
+        return HyenaDecodeState(self, batch_size, max_seqlen, dtype=dtype)
+
+    def _decode_key(self):
+        return self.layer_idx if getattr(self, "layer_idx", None) is not None else self
+
+    def _forward_cached(self, u, ip):
+        """forward(u, inference_params=ip): the prefill (ip.seqlen_offset == 0: the plain forward over the prompt, bit for bit, which also fills the
+        cache) or one step (u (B, 1, D), ip.seqlen_offset > 0: position seqlen_offset of every sequence, three kernels between the GEMVs)."""
+        from .inference import check_decodable
+        check_decodable(self)
+        st = ip.key_value_memory_dict.get(self._decode_key())
+        if st is None:
+            raise ValueError("inference_params holds no decode cache for this operator: fill key_value_memory_dict from allocate_inference_cache")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("incremental decoding is inference only: run it under torch.no_grad() / torch.inference_mode(), or freeze the parameters")
+        B, l, _ = u.shape
+        if B > st.B:
+            raise ValueError(f"a batch of {B} sequences does not fit a decode cache built for {st.B}")
+        off = int(ip.seqlen_offset)
+        if off == 0:
+            if not 1 <= l <= st.L:
+                raise ValueError(f"a prompt of {l} positions does not fit a decode cache of {st.L}")
+            y, xT, vg = self._forward_fused_cm(u, l, keep_vg=True)
+            if xT.dtype != st.dtype:
+                raise ValueError(f"the prefill runs in {xT.dtype}, the decode cache was built for {st.dtype}")
+            st.store_prefill(xT, vg, l)
+        else:
+            if l != 1:
+                raise ValueError(f"a decode step takes one position per sequence (got {l}); prefill with seqlen_offset = 0")
+            if off >= st.L:
+                raise ValueError(f"position {off} is past the decode cache's max_seqlen = {st.L}")
+            x = hyena_linear(u, self.in_proj.weight, None)                   # (B, 1, 3D): the forward's 16-bit weight shadows / autocast
+            if x.dtype != st.dtype:
+                raise ValueError(f"the step runs in {x.dtype}, the decode cache was built for {st.dtype}")
+            z = st.step(x.reshape(B, 3 * self.d_model).contiguous())
+            y = hyena_linear(z.view(B, 1, self.d_model), self.out_proj.weight, self.out_proj.bias)
+        return (y, None) if self.return_state else y
+
+    def forward(self, u, *args, inference_params=None, **kwargs):
+        if inference_params is not None:
+            return self._forward_cached(u, inference_params)
         l = u.size(-2)
         l_filter = min(l, self.l_max)
         if self._fused_ok() and l_filter <= _lib_max_l():
-            fside = _FilterOnSideStream(u, l_filter)
-            k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))           # (D, l), rows contiguous along l; on the second stream, next to in_proj
-            fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
             if CHANNEL_MAJOR:
-                # x^T = W_in u^T straight out of the GEMM (3D, B, L): nothing between the projections is ever transposed
-                # (16-bit operands at d_model 128 / 256: this package's MFMA kernel, which also hands back the conv's input v * x1
-                # from its epilogue -- csrc/proj_kernels.h; otherwise the library GEMM and vg = None)
-                xT, vg = in_proj_pre_cm(u, self.in_proj.weight, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias,
-                                        l_filter)
-                fside.join(k)
-                if l_filter > 0 and xT.shape[1] > 0 and mixer_out_supported(xT, l_filter, self.out_proj.weight):
-                    # out_proj as this package's matrix-core kernel, the `* x0` gate on its operand load (csrc/proj_kernels.h, round 4)
-                    y = hyena_mixer_out_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
-                                           vg, self.out_proj.weight, self.out_proj.bias)
-                else:
-                    zT = hyena_mixer_core_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
-                                             vg=vg)
-                    y = out_proj_cm(zT, self.out_proj.weight, self.out_proj.bias)   # activation is the identity (_fused_ok)
+                y = self._forward_fused_cm(u, l_filter)[0]
             else:
+                fside = _FilterOnSideStream(u, l_filter)
+                k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))
+                fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
                 x = hyena_linear(u, self.in_proj.weight, self.in_proj.bias)     # (B, L, 3D), hipBLASLt GEMM
                 z = hyena_mixer_core(x, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter)
                 y = hyena_linear(self.activation(z), self.out_proj.weight, self.out_proj.bias)

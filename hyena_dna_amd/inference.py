@@ -1,0 +1,128 @@
+"""Incremental decoding: the per-layer cache of ``HyenaOperator`` and flash_attn's ``InferenceParams``.
+
+Every operation of the HyenaDNA model is per-position or causal, and the implicit filter is prefix-consistent (``PositionalEmbedding`` slices
+one ``l_max``-long table), so position t of a layer's long convolution is ``sum_{s <= t} k[c, t - s] vg[b, c, s] + fb[c] vg[b, c, t]``: a
+dot product over the history of the convolution's input ``vg = v * x1``.  ``HyenaDecodeState`` holds what that takes -- the filter
+``filter_dl(max_seqlen)``, the history, the last two in_proj outputs the 3-tap short convolution still needs, the position (in device
+memory: one captured graph serves every position) and the step's small buffers -- and ``HyenaOperator.forward(u, inference_params=ip)``
+fills it with a prefill (``ip.seqlen_offset == 0``) and advances it by one position per call afterwards (csrc/decode_kernels.h).
+"""
+import torch
+
+from . import _lib
+
+__all__ = ["InferenceParams", "HyenaDecodeState", "check_decodable"]
+
+
+class InferenceParams:
+    """flash_attn.utils.generation.InferenceParams: ``max_seqlen``, ``max_batch_size``, ``seqlen_offset`` (alias ``sequence_len_offset``, the
+    older name), ``batch_size_offset``, ``key_value_memory_dict`` (layer key -> that layer's cache), ``lengths_per_sample``."""
+
+    def __init__(self, max_seqlen, max_batch_size, seqlen_offset=0, batch_size_offset=0, key_value_memory_dict=None, lengths_per_sample=None):
+        self.max_seqlen = max_seqlen
+        self.max_batch_size = max_batch_size
+        self.seqlen_offset = seqlen_offset
+        self.batch_size_offset = batch_size_offset
+        self.key_value_memory_dict = {} if key_value_memory_dict is None else key_value_memory_dict
+        self.lengths_per_sample = lengths_per_sample
+
+    @property
+    def sequence_len_offset(self):
+        return self.seqlen_offset
+
+    @sequence_len_offset.setter
+    def sequence_len_offset(self, value):
+        self.seqlen_offset = value
+
+    def reset(self, max_seqlen, max_batch_size):
+        self.max_seqlen = max_seqlen
+        self.max_batch_size = max_batch_size
+        self.seqlen_offset = 0
+        if self.lengths_per_sample is not None:
+            self.lengths_per_sample.zero_()
+
+
+def check_decodable(op, max_seqlen=None):
+    """What the decode step serves: the fused channel-major route of an order-2 causal operator, at most min(l_max, 2^20) positions.
+    Anything else is refused here, up front -- never a silent fall-back to recomputing the prefix."""
+    from . import hyena as H
+    if op.order != 2:
+        raise NotImplementedError(f"incremental decoding serves order-2 operators only (this one has order {op.order})")
+    if getattr(op.filter_fn, "bidirectional", False):
+        raise NotImplementedError("incremental decoding needs a causal filter (bidirectional=True is not causal)")
+    if not op._fused_ok() or not H.CHANNEL_MAJOR:
+        raise NotImplementedError("incremental decoding serves the fused channel-major operator route only (one head, one block, inner factor 1, "
+                                  "3 short-filter taps, no outer mixing / post-order FFN, HYENA_MIXER_LAYOUT=channel)")
+    if max_seqlen is not None:
+        limit = min(op.l_max, _lib.MAX_L)
+        if not 1 <= int(max_seqlen) <= limit:
+            raise ValueError(f"max_seqlen={max_seqlen}: the decode cache holds 1 ... {limit} positions (l_max = {op.l_max}, kernel limit 2^20)")
+
+
+def _default_dtype(op, device):
+    dev_type = device.type
+    if torch.is_autocast_enabled(dev_type):
+        dt = torch.get_autocast_dtype(dev_type)
+        if dt in (torch.bfloat16, torch.float16):
+            return dt
+    return op.in_proj.weight.dtype
+
+
+class HyenaDecodeState:
+    """The decode cache of one order-2 ``HyenaOperator`` for up to ``batch_size`` sequences of up to ``max_seqlen`` positions.
+
+    Like a key-value cache it is a SNAPSHOT of the weights it was built from: the filter ``k = filter_dl(max_seqlen)``, the short filter and
+    the biases are copied when the cache is built, the history holds activations of the weights of its time.  Build a new cache after the
+    weights change.  ``dtype``: the I/O type of the operator's activations (the autocast type, or the parameters' type); the prefill and
+    every step must run in it.
+
+    Memory: k (D, max_seqlen) fp32 + history (batch_size, D, max_seqlen) in ``dtype`` + O(B D) -- at 2^20 x 256 with B = 1 in bf16, 1 GiB
+    plus 0.5 GiB per layer."""
+
+    def __init__(self, op, batch_size, max_seqlen, dtype=None):
+        check_decodable(op, max_seqlen)
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size={batch_size}: at least one sequence")
+        dev = op.in_proj.weight.device
+        self.dtype = dtype if dtype is not None else _default_dtype(op, dev)
+        if self.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError(f"dtype={self.dtype}: the decode kernels take float32 / bfloat16 / float16 activations")
+        self.B, self.L, self.D = int(batch_size), int(max_seqlen), op.d_model
+        D, L = self.D, self.L
+        with torch.no_grad():
+            k = op.filter_fn.filter_dl(L).detach().to(torch.float32)
+            if _lib.ld_of(k) is not None and _lib.ld_of(k) % 4 == 0 and k.data_ptr() % 16 == 0 and k.shape == (D, L):
+                self.k = k
+            else:
+                self.k = torch.zeros(D, _lib.row_pitch(L), dtype=torch.float32, device=dev)[:, :L]
+                self.k.copy_(k)
+            del k
+            fb = op.filter_fn.bias if op.filter_fn.use_bias else 0 * op.filter_fn.bias
+            self.fb = fb.detach().to(torch.float32).reshape(D).clone()
+            self.bin = op.in_proj.bias.detach().to(torch.float32).clone() if op.in_proj.bias is not None else None
+            self.w = op.short_filter.weight.detach().to(torch.float32).reshape(3 * D, 3).clone()
+            self.b = op.short_filter.bias.detach().to(torch.float32).clone()
+        self.hist = torch.zeros(self.B, D, _lib.row_pitch(L), dtype=self.dtype, device=dev)
+        self.tail = torch.zeros(3 * D, self.B, 2, dtype=torch.float32, device=dev)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.x0 = torch.empty(self.B, D, dtype=torch.float32, device=dev)
+        self.z = torch.empty(self.B, D, dtype=self.dtype, device=dev)
+        self.part = _lib.decode_partials(self.B, D, L, dev)
+
+    def store_prefill(self, xT, vg, P):
+        """after the prefill forward over P positions: its convolution input vg (B, D, P) and the last two in_proj outputs of xT (3D, B, P)"""
+        B = vg.shape[0]
+        self.hist[:B, :, :P].copy_(vg)
+        n = min(P, 2)
+        self.tail[:, :B].zero_()
+        self.tail[:, :B, 2 - n:].copy_(xT[:, :, P - n:P])
+        self.pos.fill_(P)
+
+    def step(self, x2):
+        """x2 (B, 3D): in_proj output of the new position without bias -> z (B, D) for out_proj (three kernels; advances the position)"""
+        B = x2.shape[0]
+        _lib.decode_pre(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L)
+        _lib.decode_conv(self.k, self.hist, self.part, self.pos, B, self.L)
+        z = self.z[:B]
+        _lib.decode_post(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.L)
+        return z

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 from .block import dropout_add_layer_norm, embedding_dropout_add_layer_norm, embedding_fusable
 from .projection import hyena_linear
 
-__all__ = ["Mlp", "Block", "GPT2Embeddings", "MHA", "GenerationMixin", "HyenaDNALM", "sync_shared_params", "all_gather_raw"]
+__all__ = ["Mlp", "Block", "GPT2Embeddings", "MHA", "GenerationMixin", "HyenaDNALM", "GraphedDecodeStep", "sync_shared_params", "all_gather_raw"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -341,27 +341,63 @@ class Block(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------------
 # flash_attn.utils.generation.GenerationMixin / flash_attn.utils.distributed
 # ---------------------------------------------------------------------------------------------------------------------
+def _last_logits(out):
+    logits = (out[0] if isinstance(out, tuple) else out)
+    return (logits.logits if hasattr(logits, "logits") else logits)[:, -1]
+
+
+def _sample(logits, top_k, temperature):
+    logits = logits / max(temperature, 1e-6)
+    if top_k <= 1:
+        nxt = logits.argmax(-1, keepdim=True)
+    else:
+        v, i = logits.topk(top_k, dim=-1)
+        nxt = i.gather(-1, torch.multinomial(torch.softmax(v.float(), -1), 1))
+    return logits, nxt
+
+
 class GenerationMixin:
-    """Greedy / top-k sampling by re-running the causal model on the growing prefix (the convolutional mixer has no
-    incremental state in the reference either: HyenaOperator ignores ``inference_params``)."""
+    """Greedy / top-k sampling.  Default: by re-running the causal model on the growing prefix (the reference's way: its HyenaOperator
+    ignores ``inference_params``).  ``use_cache=True``: one prefill that fills every layer's decode cache, then one incremental step per
+    token (hyena_dna_amd/inference.py); ``cg=True`` in addition replays the whole per-token step as one captured hipGraph
+    (``GraphedDecodeStep``).  Sampling is the same code either way."""
 
     def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
         return None
 
     @torch.no_grad()
-    def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, **kwargs):
+    def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
+                 cg=False, **kwargs):
+        if cg and not use_cache:
+            raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
         ids, scores = input_ids, []
-        while ids.shape[1] < max_length:
-            out = self(ids)
-            logits = (out[0] if isinstance(out, tuple) else out)
-            logits = (logits.logits if hasattr(logits, "logits") else logits)[:, -1] / max(temperature, 1e-6)
-            if top_k <= 1:
-                nxt = logits.argmax(-1, keepdim=True)
-            else:
-                v, i = logits.topk(top_k, dim=-1)
-                nxt = i.gather(-1, torch.multinomial(torch.softmax(v.float(), -1), 1))
-            scores.append(logits)
-            ids = torch.cat([ids, nxt], dim=1)
+        if not use_cache:
+            while ids.shape[1] < max_length:
+                logits, nxt = _sample(_last_logits(self(ids)), top_k, temperature)
+                scores.append(logits)
+                ids = torch.cat([ids, nxt], dim=1)
+        elif ids.shape[1] < max_length:
+            from .inference import InferenceParams
+            B = ids.shape[0]
+            ip = InferenceParams(max_seqlen=max_length, max_batch_size=B)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, max_length)
+            if ip.key_value_memory_dict is None:
+                raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
+            last = _last_logits(self(ids, inference_params=ip))
+            ip.seqlen_offset = ids.shape[1]
+            step = GraphedDecodeStep(self, ip, B) if cg else None
+            try:
+                while True:
+                    logits, nxt = _sample(last, top_k, temperature)
+                    scores.append(logits)
+                    ids = torch.cat([ids, nxt], dim=1)
+                    if ids.shape[1] >= max_length:
+                        break
+                    last = step(nxt) if cg else _last_logits(self(nxt, inference_params=ip))
+                    ip.seqlen_offset += 1
+            finally:
+                if step is not None:
+                    step.release()
         if return_dict_in_generate:
             return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(ids, tuple(scores) if output_scores else None)
         return ids
@@ -446,6 +482,10 @@ class HyenaDNALM(nn.Module, GenerationMixin):
                 blk.mlp = CheckpointedModule(blk.mlp)
             if checkpoint_mixer:
                 blk.mixer = CheckpointedModule(blk.mixer)
+        for i, blk in enumerate(backbone.layers):
+            mixer = getattr(blk.mixer, "layer", blk.mixer)
+            if isinstance(mixer, HyenaOperator) and mixer.layer_idx is None:
+                mixer.layer_idx = i                       # the key of its decode cache (long_conv_lm.py:171-185 passes layer_idx the same way)
         backbone.drop_f = nn.Dropout(resid_dropout)
         backbone.ln_f = nn.LayerNorm(d_model, eps=layer_norm_epsilon)
         self.backbone = backbone
@@ -459,9 +499,12 @@ class HyenaDNALM(nn.Module, GenerationMixin):
     def tie_weights(self):
         self.lm_head.weight = self.backbone.embeddings.word_embeddings.weight
 
-    def hidden(self, input_ids, position_ids=None):
+    def hidden(self, input_ids, position_ids=None, inference_params=None):
         bb = self.backbone
         emb, blk0 = bb.embeddings, bb.layers[0]
+        # inference_params reach every mixer through the block's mixer_kwargs (long_conv_lm.py:375-378); a non-empty mixer_kwargs also keeps the
+        # block off forward_add_norm
+        mk = (lambda: None) if inference_params is None else (lambda: {"inference_params": inference_params})
         if (self.fused_dropout_add_ln and self.residual_in_fp32 and isinstance(blk0, Block) and blk0.prenorm and blk0.fused_dropout_add_ln
                 and blk0.residual_in_fp32 and emb.project_in is None and emb.max_position_embeddings <= 0
                 and embedding_fusable(input_ids, emb.word_embeddings, blk0.norm1.weight)):
@@ -473,13 +516,13 @@ class HyenaDNALM(nn.Module, GenerationMixin):
                 odt = torch.float32
             hidden_states, residual = embedding_dropout_add_layer_norm(input_ids, emb.word_embeddings.weight, blk0.norm1.weight, blk0.norm1.bias,
                                                                        blk0.dropout1.p if self.training else 0.0, blk0.norm1.eps, out_dtype=odt)
-            hidden_states, residual = blk0(hidden_states, residual, normed=True)
+            hidden_states, residual = blk0(hidden_states, residual, normed=True, mixer_kwargs=mk())
             rest = list(bb.layers)[1:]
         else:
             hidden_states, residual = emb(input_ids, position_ids=position_ids), None
             rest = bb.layers
         for blk in rest:
-            hidden_states, residual = blk(hidden_states, residual)
+            hidden_states, residual = blk(hidden_states, residual, mixer_kwargs=mk())
         if self.fused_dropout_add_ln:
             return dropout_add_layer_norm(hidden_states, residual, bb.ln_f.weight, bb.ln_f.bias,
                                           bb.drop_f.p if self.training else 0.0, bb.ln_f.eps, prenorm=False,
@@ -519,9 +562,26 @@ class HyenaDNALM(nn.Module, GenerationMixin):
                 return L
         return Lp
 
+    def _mixers(self):
+        return [getattr(blk.mixer, "layer", blk.mixer) for blk in self.backbone.layers]      # (a CheckpointedModule is unwrapped)
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        """{layer key: HyenaDecodeState} for InferenceParams.key_value_memory_dict (flash_attn's generate assigns it that way).  Every layer must
+        be servable (HyenaOperator._forward_cached's refusals apply here, up front).  The caches are snapshots of the weights at this call."""
+        return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype) for m in self._mixers()}
+
     def forward(self, input_ids, position_ids=None, inference_params=None, state=None):
         # (the head through projection.hyena_linear: its weight gradient contracts 16 x 256 outputs over 10^6 tokens, which the GEMM library
         # runs on 16 workgroups -- 1.19 ms per step at 2^20 tokens, profiles/r4y_model_stats.csv -- and the split-K form does not)
+        if inference_params is not None:
+            # incremental decoding: the prompt as it is (padding would put positions into the cache), then one position per call
+            emb = self.backbone.embeddings
+            if position_ids is None and emb.max_position_embeddings > 0:
+                off = int(inference_params.seqlen_offset)
+                position_ids = torch.arange(off, off + input_ids.shape[1], dtype=torch.long, device=input_ids.device)
+            hidden = self.hidden(input_ids, position_ids, inference_params=inference_params)
+            lm_logits = hyena_linear(hidden, self.lm_head.weight, self.lm_head.bias)
+            return namedtuple("CausalLMOutput", ["logits"])(logits=lm_logits), None
         L = input_ids.shape[1]
         Lp = self._aligned_length(input_ids) if position_ids is None else L
         if Lp != L:
@@ -556,7 +616,9 @@ class CheckpointedModule(nn.Module):
         super().__init__()
         self.layer = layer
 
-    def forward(self, x):
+    def forward(self, x, **kwargs):
+        if kwargs.get("inference_params") is not None:        # inference: nothing to recompute, the wrapped module runs as it is
+            return self.layer(x, **kwargs)
         from torch.utils.checkpoint import checkpoint
         return checkpoint(self.layer, x, use_reentrant=False)
 
@@ -674,3 +736,70 @@ class GraphedTrainStep:
             self.targets.copy_(targets, non_blocking=True)
         self.graph.replay()
         return self.loss
+
+
+class GraphedDecodeStep:
+    """The whole per-token step of cached generation -- embedding of a static (B, 1) token buffer, every layer's decode step, ln_f, the
+    head -- captured into ONE hipGraph after the prefill and replayed once per token (``generate(use_cache=True, cg=True)``).  At short
+    contexts the eager step is a few dozen launches of almost no work each; a replay is one.  The decode kernels read the position from
+    device memory, so the one graph serves every position; sampling stays outside.
+
+        step = GraphedDecodeStep(model, ip, batch_size)      # after the prefill: warms up on the capture stream, captures
+        logits = step(next_tokens)                           # (B, V) static buffer, overwritten by the next replay
+        step.release()
+
+    Warm-up steps run the real kernels: the cache's tail state and position are put back afterwards (the history column they wrote is
+    rewritten by the first replay).  Same preconditions as ``GraphedTrainStep`` (``hyena_dna_amd.prepare_graph_runtime()``)."""
+
+    def __init__(self, model, inference_params, batch_size, warmup=2):
+        import hyena_dna_amd
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("GraphedDecodeStep captures a hipGraph: the model must live on a ROCm device")
+        if not hyena_dna_amd.GRAPH_SAFE or os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE") != "0":
+            raise RuntimeError("GraphedDecodeStep: hipGraph replays are only reliable on this ROCm runtime with DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 "
+                               "in the environment before the HIP runtime initialises (hyena_dna_amd.prepare_graph_runtime(); INTEGRATION.md "
+                               "section 6)")
+        self.model, self.ip = model, inference_params
+        self.ids = torch.zeros(batch_size, 1, dtype=torch.long, device=dev)
+        emb = model.backbone.embeddings
+        self.pos_ids = torch.zeros(1, dtype=torch.long, device=dev) if emb.max_position_embeddings > 0 else None
+        states = list(inference_params.key_value_memory_dict.values())
+        side = torch.cuda.Stream(dev)
+        self._side = side
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            snap = [(s.tail.clone(), s.pos.clone()) for s in states]
+            for _ in range(max(1, int(warmup))):
+                self._run()
+            for s, (tail, pos) in zip(states, snap):
+                s.tail.copy_(tail)
+                s.pos.copy_(pos)
+            side.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=side):
+                self.logits = self._run()
+        torch.cuda.current_stream(dev).wait_stream(side)
+
+    def _run(self):
+        out = self.model(self.ids, position_ids=self.pos_ids, inference_params=self.ip)
+        return out[0].logits[:, -1]
+
+    def __call__(self, input_ids):
+        """replays the step for the tokens input_ids (B, 1) at position ip.seqlen_offset; returns the static (B, V) logits"""
+        self.ids.copy_(input_ids, non_blocking=True)
+        if self.pos_ids is not None:
+            self.pos_ids.fill_(int(self.ip.seqlen_offset))
+        self.graph.replay()
+        return self.logits
+
+    def release(self):
+        if self.graph is None:
+            return
+        from . import _lib
+        dev = self.ids.device
+        self.graph = None
+        self.logits = None
+        torch.cuda.synchronize(dev)
+        _lib.release_stream_state(dev, self._side.cuda_stream)
+        self._side = None
