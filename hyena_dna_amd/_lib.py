@@ -538,6 +538,29 @@ def save_spectra_default(B, D, L, device=None):
     return hit
 
 
+def fftconv_fwd_keep(u, k, bias, want_grad, keep=None):
+    """The forward convolution of an autograd forward -> (out, spectra or None).  What it keeps for the backward -- the column spectra when any
+    gradient is wanted and save_spectra_default agrees (time-for-memory trade), otherwise nothing: the backward then recomputes them from
+    (u, k) -- is decided here for every caller.  keep: the decision, where it has been taken already (a chain of convolutions of one shape
+    takes it once)."""
+    if keep is None:
+        keep = want_grad and save_spectra_default(*u.shape, device=u.device)
+    if keep:
+        return fftconv_fwd(u, k, bias, save=True)
+    return fftconv_fwd(u, k, bias, grad=want_grad), None
+
+
+def spectra_hold_input(L):
+    """Do the spectra fftconv_fwd(save=True) keeps at this length hold the transform of the convolution's input?  The two-level plan's do; the
+    on-chip plan (L <= 32768) keeps the filter's spectrum alone."""
+    return lib().hyena_fftconv_plan(int(L)) != PLAN_ONCHIP
+
+
+def bwd_needs_input(spectra, L):
+    """Does fftconv_bwd(..., saved=spectra) read the convolution's input u again (so that a caller who did not keep it has to recompute it)?"""
+    return spectra is None or not spectra_hold_input(L)
+
+
 def fftconv_fwd(u, k, bias, chunk=None, save=False, grad=None):
     """u (B, D, L), k (D, L) fp32, bias (D,) fp32 or None -> out like u.  u and k may be packed or pitched rows (ld_of); out gets u's pitch.
     save=True additionally returns the saved-spectrum buffer for fftconv_bwd(..., saved=).

@@ -90,15 +90,7 @@ class FFTConvFunc(torch.autograd.Function):
             if D.numel() != H:
                 raise ValueError(f"D must have {H} elements, got shape {tuple(D.shape)}")
             bias = D.detach().to(torch.float32).reshape(H).contiguous()
-        # keep the forward's column spectra for the backward when any gradient is wanted (time-for-memory trade,
-        # _lib.save_spectra_default); otherwise the backward recomputes them from (u, k)
-        want_grad = any(_gradmode.needs(ctx)[:3])
-        saved = None
-        if want_grad and _lib.save_spectra_default(*rows.shape, device=rows.device):
-            out, saved = _lib.fftconv_fwd(rows, kf, bias, save=True)
-        else:
-            out = _lib.fftconv_fwd(rows, kf, bias, grad=want_grad)
-        ctx.spectra = saved
+        out, ctx.spectra = _lib.fftconv_fwd_keep(rows, kf, bias, any(_gradmode.needs(ctx)[:3]))
         ctx.save_for_backward(rows, kf, bias if bias is not None else torch.empty(0, device=u.device))
         ctx.has_bias = bias is not None
         ctx.restore = restore

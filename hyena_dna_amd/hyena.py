@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .fftconv import fftconv_func, fftconv_ref
 from .filter import fused_filter_ok, hyena_filter_dl
-from .mixer import hyena_mixer_core, hyena_mixer_core_cm, hyena_mixer_core_cm_order_n, hyena_mixer_out_cm, mixer_out_supported
+from .mixer import hyena_mixer_core, hyena_mixer_core_cm, hyena_mixer_core_cm_order_n, hyena_mixer_out_cm, mixer_out_supported, shell_operands
 from .projection import hyena_linear, in_proj_cm, in_proj_pre_cm, out_proj_cm
 
 # Layout of the tensors between the operator's two projections: channel-major (x^T written by the in_proj GEMM, z^T read by
@@ -287,13 +287,17 @@ class HyenaFilter(_OptimModule):
             return False
         return fused_filter_ok(L, z.shape[-1], lin[0].out_features, out_channels or lin[3].out_features, 2, self.normalized, False)
 
+    def conv_bias(self, bias=None):
+        """The long convolution's bias D (the ``+ u * D`` term): the parameter, or the caller's tensor; with ``bias=False`` zeros -- as a product,
+        so that the result stays connected to it."""
+        bias = self.bias if bias is None else bias
+        return bias if self.use_bias else 0 * bias
+
     def forward(self, x, L, k=None, bias=None, *args, **kwargs):
         if k is None:
             k = self.filter(L)
         k = k[0] if type(k) is tuple else k
-        if bias is None:
-            bias = self.bias
-        bias = bias if self.use_bias else 0 * bias
+        bias = self.conv_bias(bias)
         if self.bidirectional:
             # hyena.py:67-73 (README "Experimental"): the input centred in the 2L window = the causal result delayed by L // 2
             y = fftconv_ref(x, k, bias.to(dtype=torch.float32), dropout_mask=None, gelu=False, bidirectional=True)
@@ -398,11 +402,7 @@ class HyenaOperator(nn.Module):
             return None
         if not (u.is_cuda or not _fused_filter_requires_gpu()) or not _add_norm_fused(self.d_model):
             return None
-        fside = _FilterOnSideStream(u, l_filter)
-        k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))
-        fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
-        xT, vg = in_proj_pre_cm(u, self.in_proj.weight, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, l_filter)
-        fside.join(k)
+        (k,), fb, xT, vg = self._filters_and_in_proj(u, l_filter)
         if not mixer_out_supported(xT, l_filter, self.out_proj.weight):
             # (xT is already made: finish on the unfused route so that nothing is computed twice)
             zT = hyena_mixer_core_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter, vg=vg)
@@ -412,24 +412,35 @@ class HyenaOperator(nn.Module):
         return hyena_mixer_out_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter, vg,
                                   self.out_proj.weight, self.out_proj.bias, add_norm=(residual, norm_weight, norm_bias, eps))
 
+    def _filters_and_in_proj(self, u, l_filter):
+        """What every fused route opens with -> (ks, fb, x, vg).  ks: the order - 1 filters (D, l), rows contiguous along l, evaluated on the
+        second stream next to the in-projection and joined (_FilterOnSideStream); fb: the convolution bias; x: the in-projection in the route's
+        layout --
+        channel-major, order 2: x^T = W_in u^T (3D, B, L) without the bias, straight out of the GEMM: nothing between the projections is ever
+            transposed (16-bit operands at d_model 128 / 256: this package's MFMA kernel, which also hands back the conv's input vg = v * x1
+            from its epilogue -- csrc/proj_kernels.h; otherwise the library GEMM and vg = None)
+        channel-major, order >= 3: x^T ((order + 1) D, B, L) from the library GEMM, bias added on load by the shell kernels
+        position-major: x (B, L, 3D) with the bias, hipBLASLt GEMM"""
+        fside = _FilterOnSideStream(u, l_filter)
+        ks = fside.run(lambda: self.filter_fn.filter_dl_split(l_filter, self.order - 1))     # ('(v o)' channels, hyena.py:408)
+        fb = self.filter_fn.conv_bias()
+        vg = None
+        if not CHANNEL_MAJOR:
+            x = hyena_linear(u, self.in_proj.weight, self.in_proj.bias)
+        elif self.order == 2:
+            x, vg = in_proj_pre_cm(u, self.in_proj.weight, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, l_filter)
+        else:
+            x = in_proj_cm(u, self.in_proj.weight)
+        fside.join(ks)
+        return ks, fb, x, vg
+
     def _forward_fused_cm(self, u, l_filter, keep_vg=False):
         """the fused channel-major route -> (y, xT, vg).  keep_vg: vg is made here (cm_pre_fwd on xT, what the mixer would run itself) when
         the projection kernel does not hand it back -- the same kernel on the same operands, so y does not change by a bit."""
-        fside = _FilterOnSideStream(u, l_filter)
-        k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))           # (D, l), rows contiguous along l; on the second stream, next to in_proj
-        fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
-        # x^T = W_in u^T straight out of the GEMM (3D, B, L): nothing between the projections is ever transposed
-        # (16-bit operands at d_model 128 / 256: this package's MFMA kernel, which also hands back the conv's input v * x1
-        # from its epilogue -- csrc/proj_kernels.h; otherwise the library GEMM and vg = None)
-        xT, vg = in_proj_pre_cm(u, self.in_proj.weight, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias,
-                                l_filter)
-        fside.join(k)
+        (k,), fb, xT, vg = self._filters_and_in_proj(u, l_filter)
         if keep_vg and vg is None:
             from . import _lib
-            D3 = xT.shape[0]
-            vg = _lib.cm_pre_fwd(_lib.as_cm(xT), self.in_proj.bias.detach().to(torch.float32).contiguous(),
-                                 self.short_filter.weight.detach().to(torch.float32).reshape(D3, 3).contiguous(),
-                                 self.short_filter.bias.detach().to(torch.float32).contiguous(), l_filter)
+            vg = _lib.cm_pre_fwd(_lib.as_cm(xT), *shell_operands(self.in_proj.bias, self.short_filter.weight, self.short_filter.bias), l_filter)
         if l_filter > 0 and xT.shape[1] > 0 and mixer_out_supported(xT, l_filter, self.out_proj.weight):
             # out_proj as this package's matrix-core kernel, the `* x0` gate on its operand load (csrc/proj_kernels.h, round 4)
             y = hyena_mixer_out_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
@@ -489,25 +500,18 @@ class HyenaOperator(nn.Module):
             return self._forward_cached(u, inference_params)
         l = u.size(-2)
         l_filter = min(l, self.l_max)
-        if self._fused_ok() and l_filter <= _lib_max_l():
-            if CHANNEL_MAJOR:
-                y = self._forward_fused_cm(u, l_filter)[0]
-            else:
-                fside = _FilterOnSideStream(u, l_filter)
-                k = fside.run(lambda: self.filter_fn.filter_dl(l_filter))
-                fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
-                x = hyena_linear(u, self.in_proj.weight, self.in_proj.bias)     # (B, L, 3D), hipBLASLt GEMM
-                z = hyena_mixer_core(x, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter)
-                y = hyena_linear(self.activation(z), self.out_proj.weight, self.out_proj.bias)
-            return (y, None) if self.return_state else y
-        if self._route(l) == "order_n":
-            fside = _FilterOnSideStream(u, l_filter)
-            ks = fside.run(lambda: self.filter_fn.filter_dl_split(l_filter, self.order - 1))   # one (D, l) filter per convolution ('(v o)' channels, hyena.py:408)
-            fb = self.filter_fn.bias if self.filter_fn.use_bias else 0 * self.filter_fn.bias
-            xT = in_proj_cm(u, self.in_proj.weight)                             # ((order + 1) D, B, L), bias added on load by the shell kernels
-            fside.join(ks)
+        route = self._route(l)
+        if route == "fused" and CHANNEL_MAJOR:
+            y = self._forward_fused_cm(u, l_filter)[0]
+        elif route == "fused":
+            (k,), fb, x, _ = self._filters_and_in_proj(u, l_filter)
+            z = hyena_mixer_core(x, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter)
+            y = hyena_linear(self.activation(z), self.out_proj.weight, self.out_proj.bias)
+        elif route == "order_n":
+            ks, fb, xT, _ = self._filters_and_in_proj(u, l_filter)
             zT = hyena_mixer_core_cm_order_n(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, ks, fb, l_filter, self.order)
             y = out_proj_cm(zT, self.out_proj.weight, self.out_proj.bias)
+        if route != "generic":
             return (y, None) if self.return_state else y
         u = self.in_proj(u).transpose(1, 2)                                     # b l d -> b d l
         uc = self.short_filter(u)[..., :l_filter]

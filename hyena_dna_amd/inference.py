@@ -97,8 +97,7 @@ class HyenaDecodeState:
                 self.k = torch.zeros(D, _lib.row_pitch(L), dtype=torch.float32, device=dev)[:, :L]
                 self.k.copy_(k)
             del k
-            fb = op.filter_fn.bias if op.filter_fn.use_bias else 0 * op.filter_fn.bias
-            self.fb = fb.detach().to(torch.float32).reshape(D).clone()
+            self.fb = op.filter_fn.conv_bias().detach().to(torch.float32).reshape(D).clone()
             self.bin = op.in_proj.bias.detach().to(torch.float32).clone() if op.in_proj.bias is not None else None
             self.w = op.short_filter.weight.detach().to(torch.float32).reshape(3 * D, 3).clone()
             self.b = op.short_filter.bias.detach().to(torch.float32).clone()

@@ -322,10 +322,8 @@ class InProjPreCMFunc(torch.autograd.Function):
             u, Lx = up, pad_to
         ctx.save_for_backward(u.reshape(B * Lx, K), weight)
         ctx.ushape = u.shape
-        bi = None if b_in is None else b_in.detach().to(torch.float32).contiguous()
-        w = sf_weight.detach().to(torch.float32).reshape(weight.shape[0], 3).contiguous()
-        b = sf_bias.detach().to(torch.float32).contiguous()
-        xT, vg = _lib.inproj_pre_fwd(u, weight, bi, w, b, L)
+        from .mixer import shell_operands
+        xT, vg = _lib.inproj_pre_fwd(u, weight, *shell_operands(b_in, sf_weight, sf_bias), L)
         ctx.mark_non_differentiable(vg)
         # (otherwise autograd hands backward a zero tensor for vg's "gradient": a 512 MB fill per layer at L = 2^20)
         ctx.set_materialize_grads(False)
@@ -390,16 +388,22 @@ class OutProjCMFunc(torch.autograd.Function):
         K, B, L = zT.shape
         rows = B * L
         dy2 = dy.reshape(rows, n)
-        dz = dw = db = None
+        dz = None
         if ctx.needs_input_grad[0]:
             dz = cm_from_pm(weight.t(), dy2, B, L)                            # (K, B, L): channel-major, straight from the GEMM
         wdt, bdt, dt = ctx.ptypes
-        if ctx.needs_input_grad[1]:
-            dw = _castcache.wgrad_out(wgrad_pm_cm(dy2, zT), wdt, dt)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            from . import _lib
-            db = _castcache.wgrad_out(_lib.colsum(dy2.contiguous()), bdt, dt if dt is not None else dy.dtype)
+        dw, db = out_proj_param_grads(dy2, zT if ctx.needs_input_grad[1] else None, wdt,
+                                      bdt if ctx.has_bias and ctx.needs_input_grad[2] else None, dt)
         return dz, dw, db, None
+
+
+def out_proj_param_grads(dy2, zT, wdt, bdt, dt):
+    """(dW, db) of y = zT^T W^T + b from dy2 (B L, N), in the parameters' types wdt / bdt; zT None / bdt None: that gradient is not wanted.
+    dt: the compute type the parameters were used in (None: the operands as they came)"""
+    from . import _lib
+    dw = None if zT is None else _castcache.wgrad_out(wgrad_pm_cm(dy2, zT), wdt, dt)
+    db = None if bdt is None else _castcache.wgrad_out(_lib.colsum(dy2.contiguous()), bdt, dt if dt is not None else dy2.dtype)
+    return dw, db
 
 
 def _autocast_dtype(x):
