@@ -51,6 +51,8 @@ def prepare_graph_runtime():
 
 
 from . import _lib  # noqa: F401,E402
+from ._castcache import invalidate as invalidate_cast_cache  # noqa: F401,E402  (after a parameter write that moves no version counter: _castcache.py)
 
-__all__ = ["fftconv", "hyena", "mixer", "filter", "projection", "block", "tokenizer", "build", "prepare_graph_runtime", "GRAPH_SAFE"]
+__all__ = ["fftconv", "hyena", "mixer", "filter", "projection", "block", "tokenizer", "build", "prepare_graph_runtime", "GRAPH_SAFE",
+           "invalidate_cast_cache"]
 __version__ = "0.1.0"

@@ -7,7 +7,10 @@ weight gradient is rounded to the 16-bit type and converted back for the fp32 ``
 
 ``shadow(p, dtype)`` is a 16-bit copy of parameter ``p`` that is refreshed for ALL registered parameters at once -- one ``torch._foreach_copy_`` -- the
 first time any of them is asked for after a change (the version counter of a tensor moves with every in-place update: optimizer steps,
-``load_state_dict``, ``copy_``; a re-allocated parameter shows in its data pointer).  Values: exactly ``p.detach().to(dtype)``.  ``rounded_f32(p, dtype)``:
+``load_state_dict``, ``copy_``; a re-allocated parameter shows in its data pointer).  Values: exactly ``p.detach().to(dtype)``.
+What moves NEITHER is not seen: an in-place write through ``p.data`` (``p.data.mul_(2)``: ``.data`` is a tensor with a version counter of its own) and a
+hipGraph replay that updates the parameters on the device.  After such a write call ``invalidate()`` (``hyena_dna_amd.invalidate_cast_cache()``);
+``lm.GraphedTrainStep`` does so after every replay.  ``rounded_f32(p, dtype)``:
 those values back in fp32 (what a bias rounded "as autocast rounds it" is added as), refreshed in the same pass.
 
 The autograd functions of this package (projection.py, mixer.py, lm.FusedMlpFunc) take the fp32 PARAMETER and look its shadow up in their forward;
@@ -50,8 +53,10 @@ def reset():
 
 
 def invalidate():
-    """mark every shadow stale: the next use refreshes them all in one pass (lm.GraphedTrainStep calls this right before its capture, so that the
-    refresh is PART of the captured step -- a shadow that happened to be fresh at capture time would never be refreshed by the replays)"""
+    """mark every shadow stale: the next use refreshes them all in one pass.  Host-only, nothing is launched.  For the callers whose parameter writes
+    the version counters do not show (module docstring); also reachable as ``hyena_dna_amd.invalidate_cast_cache``.  lm.GraphedTrainStep calls this right
+    before its capture, so that the refresh is PART of the captured step -- a shadow that happened to be fresh at capture time would never be refreshed
+    by the replays -- and after every replay, whose optimizer update no counter shows"""
     for e in _entries.values():
         e.version = -1
 

@@ -539,7 +539,9 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         are dropped before anybody sees them, so they receive zero gradients and contribute nothing to any weight gradient.  What it buys: inside a
         channel row of the flattened (C, B L) layout the rows of odd-length sequences start 2 bytes off every 4 / 16-byte boundary -- one layer at
         32767 x 8 ran 11 % slower than at 32768 x 8, the step at 1023 x 256 x 128 6 % slower (profiles/r6a_bench_default.json).  Only when every
-        layer's l_max admits the padded length (hg38 configurations: l_max = max_length + 2) and the fused kernels are in use."""
+        layer's l_max admits the padded length (hg38 configurations: l_max = max_length + 2) and the fused kernels are in use -- and only for a
+        CAUSAL stack: a bidirectional filter (HyenaFilter(bidirectional=True)) centres the input in a 2 L window, so the padded length moves every
+        output; a mixer that is not a HyenaOperator is not known to be causal.  Such models run at the length they are given."""
         B, L = input_ids.shape
         # ONE odd-length sequence: its rows are aligned (pitched), what is left are the library weight-gradient products over an odd number of
         # positions (2^20 - 1: dW1 712 vs 612 us, dW_in 611 vs 571, dW_out 303 vs 260 per layer: profiles/r6_wgrad_plan.txt).  Padded where that
@@ -556,9 +558,11 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         emb = self.backbone.embeddings
         if emb.max_position_embeddings > 0 and Lp > emb.max_position_embeddings:
             return L
-        for blk in self.backbone.layers:
-            mixer = getattr(blk.mixer, "layer", blk.mixer)
-            if getattr(mixer, "l_max", Lp) < Lp:
+        from .hyena import HyenaOperator
+        for mixer in self._mixers():
+            if not isinstance(mixer, HyenaOperator) or getattr(mixer.filter_fn, "bidirectional", False):
+                return L
+            if mixer.l_max < Lp:
                 return L
         return Lp
 
@@ -710,11 +714,12 @@ class GraphedTrainStep:
     def release(self):
         """Drop the graph and what the long-convolution binding keeps for its capture stream (workspace, tables stay: they are per length).
         Call before building the next GraphedTrainStep of a sequence-length stage."""
-        from . import _lib
+        from . import _castcache, _lib
         dev = self.ids.device
         self.graph = None
         self.loss = None
         torch.cuda.synchronize(dev)
+        _castcache.invalidate()                        # the shadows hold the weights of BEFORE the last replay's update (see __call__)
         _lib.release_stream_state(dev, self._side.cuda_stream)
         self._side = None
 
@@ -735,6 +740,11 @@ class GraphedTrainStep:
         if targets is not None:
             self.targets.copy_(targets, non_blocking=True)
         self.graph.replay()
+        # The replay refreshed the 16-bit weight shadows (the refresh is part of the captured step) and THEN updated the parameters, on the
+        # device: neither their version counters nor their addresses moved, so to _castcache the shadows look fresh while they are one
+        # optimizer step old.  Host-only (a loop over the entries, nothing is launched): eager work between two replays casts again.
+        from . import _castcache
+        _castcache.invalidate()
         return self.loss
 
 

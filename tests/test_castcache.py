@@ -62,3 +62,33 @@ def test_linear_under_autocast_semantics_with_and_without_the_cache(monkeypatch)
         else:
             assert torch.allclose(w.grad, exact_w, rtol=1e-5, atol=1e-5)
         assert torch.allclose(w.grad, gref[1], rtol=2e-2, atol=2e-2) and torch.allclose(b.grad, gref[2], rtol=2e-2, atol=5e-2)
+
+
+def test_invalidate_after_a_write_the_version_counter_does_not_show(monkeypatch):
+    """An in-place write through ``.data`` changes a parameter's storage and moves neither ``p._version`` nor ``p.data_ptr()`` -- as a hipGraph replay
+    of an optimizer step does (lm.GraphedTrainStep).  The cache cannot see it; ``invalidate()`` -- ``hyena_dna_amd.invalidate_cast_cache`` from the
+    package root -- is what such a writer calls, and after it the shadows are exactly ``p.to(dtype)`` again."""
+    import hyena_dna_amd
+    assert hyena_dna_amd.invalidate_cast_cache is CC.invalidate and "invalidate_cast_cache" in hyena_dna_amd.__all__
+    monkeypatch.setattr(CC, "ENABLED", True)
+    CC.reset()
+    torch.manual_seed(1)
+    p, q = torch.nn.Parameter(torch.randn(5, 3)), torch.nn.Parameter(torch.randn(4))
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(CC.shadow(p, dt), p.detach().to(dt)) and torch.equal(CC.rounded_f32(q, dt), q.detach().to(dt).float())
+        assert torch.equal(CC.shadow(q, dt), q.detach().to(dt))
+    v, ptr = (p._version, q._version), (p.data_ptr(), q.data_ptr())
+    p.data.mul_(2.0)
+    q.data.add_(1.0)
+    assert (p._version, q._version) == v and (p.data_ptr(), q.data_ptr()) == ptr          # the premise: nothing the cache looks at has moved
+    hyena_dna_amd.invalidate_cast_cache()
+    n0 = CC.stats()["bulk_refreshes"]
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(CC.shadow(p, dt), p.detach().to(dt))
+        assert torch.equal(CC.shadow(q, dt), q.detach().to(dt))
+        assert torch.equal(CC.rounded_f32(q, dt), q.detach().to(dt).float())
+    assert CC.stats()["bulk_refreshes"] == n0 + 2                                          # one pass per compute type, nothing per tensor
+    # re-assigning .data is the case the data pointer does catch, without any call
+    p.data = torch.randn(5, 3)
+    assert torch.equal(CC.shadow(p, torch.bfloat16), p.detach().to(torch.bfloat16))
+    CC.reset()
