@@ -10,6 +10,7 @@ HazyResearch/hyena-dna, nothing else.
 * ``hyena_dna_amd.projection``  ``in_proj`` / ``out_proj`` with a slice-batched weight gradient
 * ``hyena_dna_amd.block``    ``dropout_add_layer_norm`` (the block's residual add + LayerNorm, fused)
 * ``hyena_dna_amd.tokenizer``  vectorised DNA character tokenisation (the input side)
+* ``hyena_dna_amd.classifier``  sequence classification on the backbone (``DNAEmbeddingModel``, ``SequenceDecoder``, fused pooled readout)
 * ``hyena_dna_amd.csrc``     the HIP kernels and the C ABI (``include/hyena_fftconv.h``, ``hyena_mixer.h``, ``hyena_filter.h``)
 
 There is no CPU or PyTorch fallback for the convolution: without the compiled gfx950 library the ops raise.

@@ -290,6 +290,17 @@ def lib():
         L.hyena_add_norm_bwd.restype = c_int
         L.hyena_add_norm_bwd.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]
+        L.hyena_add_norm_pool_supported.restype = c_int
+        L.hyena_add_norm_pool_supported.argtypes = [c_int, c_int]
+        L.hyena_add_norm_pool_partial_floats.restype = c_size_t
+        L.hyena_add_norm_pool_partial_floats.argtypes = [c_int, c_long, c_int]
+        L.hyena_add_norm_pool_fwd.restype = c_int
+        L.hyena_add_norm_pool_fwd.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]
+        L.hyena_add_norm_pool_bwd.restype = c_int
+        L.hyena_add_norm_pool_bwd.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int,
+                                              c_void_p]
         if L.hyena_fftconv_abi_version() != ABI_VERSION:
             raise HyenaLibraryError(f"{LIB_PATH}: ABI version {L.hyena_fftconv_abi_version()} != {ABI_VERSION}; rebuild")
         _lib = L
@@ -1119,6 +1130,78 @@ def add_norm_bwd(dout, d_res_out, res_out, weight, mean, rstd, dx_dtype, need_dr
                                                       seed.data_ptr() if dropout_p > 0.0 else None, dx.data_ptr(), dtype_code(dx_dtype),
                                                       None if dres is None else dres.data_ptr(), dw.data_ptr(), db.data_ptr(),
                                                       None if cs is None else cs.data_ptr(), part.data_ptr(), rows, D, _backend.stream(dev)))
+    if want:
+        _gradsum.offer(dx, cs)
+    return dx, dres, dw, db
+
+
+# ---- add + LayerNorm + pooled readout of a sequence classifier (include/hyena_block.h, hyena_add_norm_pool_*) ----------
+POOL_MODES = {"mean": 0, "sum": 1}
+
+
+def add_norm_pool_supported(D, x_dtype):
+    try:
+        return bool(lib().hyena_add_norm_pool_supported(int(D), dtype_code(x_dtype)))
+    except TypeError:
+        return False
+
+
+def _pool_lengths(lengths, B, device):
+    if lengths is None:
+        return None
+    assert lengths.dtype == torch.int32 and lengths.shape == (B,) and lengths.device == device and lengths.is_contiguous()
+    return lengths
+
+
+def add_norm_pool_fwd(x0, residual, weight, bias, eps, lengths=None, mode="mean", dropout_p=0.0, seed=None):
+    """x0 (B, L, D), residual (B, L, D) fp32 or None, lengths (B,) int32 on x0's device or None -> pooled (B, D) fp32 =
+    scale_b * sum_{t < n_b} LayerNorm(dropout(x0) + residual), mean, rstd (B L,): neither the normalised tensor nor residual' is written."""
+    _require_gpu(x0, "x0")
+    if dropout_p > 0.0:
+        assert seed is not None and seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == x0.device
+    B, L, D = x0.shape
+    dev = x0.device
+    lengths = _pool_lengths(lengths, B, dev)
+    pooled = torch.zeros((B, D), dtype=torch.float32, device=dev) if B * L == 0 else torch.empty((B, D), dtype=torch.float32, device=dev)
+    mean = torch.empty(B * L, dtype=torch.float32, device=dev)
+    rstd = torch.empty(B * L, dtype=torch.float32, device=dev)
+    if B * L == 0:
+        return pooled, mean, rstd
+    part = torch.empty(lib().hyena_add_norm_pool_partial_floats(B, L, D) // 3, dtype=torch.float32, device=dev)
+    with _backend.guard(dev):
+        check(lib().hyena_add_norm_pool_fwd(x0.data_ptr(), dtype_code(x0.dtype), None if residual is None else residual.data_ptr(),
+                                            weight.data_ptr(), bias.data_ptr(), float(eps), float(dropout_p),
+                                            seed.data_ptr() if dropout_p > 0.0 else None, None if lengths is None else lengths.data_ptr(),
+                                            POOL_MODES[mode], pooled.data_ptr(), mean.data_ptr(), rstd.data_ptr(), part.data_ptr(), B, L, D,
+                                            _backend.stream(dev)))
+    return pooled, mean, rstd
+
+
+def add_norm_pool_bwd(g, x0, residual, weight, mean, rstd, lengths=None, mode="mean", need_dres=True, dropout_p=0.0, seed=None,
+                      offer_colsum=True):
+    """g (B, D) fp32, the gradient of pooled -> dx0 (B L, D) x0's dtype, d_residual (B L, D) fp32 or None, dweight (D,), dbias (D,); no
+    (B, L, D) dout exists.  offer_colsum: as in add_norm_bwd (the bias gradient of the linear layer in front of this norm)."""
+    _require_gpu(g, "g")
+    B, L, D = x0.shape
+    dev = x0.device
+    lengths = _pool_lengths(lengths, B, dev)
+    dx = torch.empty((B * L, D), dtype=x0.dtype, device=dev)
+    dres = torch.empty((B * L, D), dtype=torch.float32, device=dev) if need_dres else None
+    if B * L == 0:
+        return dx, dres, torch.zeros(D, dtype=torch.float32, device=dev), torch.zeros(D, dtype=torch.float32, device=dev)
+    dw = torch.empty(D, dtype=torch.float32, device=dev)
+    db = torch.empty(D, dtype=torch.float32, device=dev)
+    part = torch.empty(lib().hyena_add_norm_pool_partial_floats(B, L, D), dtype=torch.float32, device=dev)
+    from . import _gradsum
+    want = offer_colsum and _gradsum.ENABLED and x0.dtype in (torch.bfloat16, torch.float16)
+    cs = torch.empty(D, dtype=torch.float32, device=dev) if want else None
+    with _backend.guard(dev):
+        check(lib().hyena_add_norm_pool_bwd(g.data_ptr(), x0.data_ptr(), dtype_code(x0.dtype), None if residual is None else residual.data_ptr(),
+                                            weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), float(dropout_p),
+                                            seed.data_ptr() if dropout_p > 0.0 else None, None if lengths is None else lengths.data_ptr(),
+                                            POOL_MODES[mode], dx.data_ptr(), None if dres is None else dres.data_ptr(), dw.data_ptr(),
+                                            db.data_ptr(), None if cs is None else cs.data_ptr(), part.data_ptr(), B, L, D,
+                                            _backend.stream(dev)))
     if want:
         _gradsum.offer(dx, cs)
     return dx, dres, dw, db

@@ -19,7 +19,8 @@ import torch.nn.functional as F
 
 from . import _lib
 
-__all__ = ["dropout_add_layer_norm", "AddLayerNormFunc", "embedding_dropout_add_layer_norm", "embedding_fusable"]
+__all__ = ["dropout_add_layer_norm", "AddLayerNormFunc", "embedding_dropout_add_layer_norm", "embedding_fusable",
+           "dropout_add_layer_norm_pool", "AddNormPoolFunc"]
 
 
 class AddLayerNormFunc(torch.autograd.Function):
@@ -134,3 +135,78 @@ def dropout_add_layer_norm(x0, residual, weight, bias, dropout_p, epsilon, rowsc
         res = res.to(torch.float32)
     out = F.layer_norm(res.to(weight.dtype), (x0.shape[-1],), weight, bias, epsilon).to(x0.dtype)
     return (out, res) if prenorm else out
+
+
+class AddNormPoolFunc(torch.autograd.Function):
+    """pooled (B, D) fp32 = scale_b * sum_{t < n_b} LayerNorm(dropout(x0) + residual)[b, t] in one pass over x0 and residual (include/hyena_block.h,
+    hyena_add_norm_pool_*): the normalised (B, L, D) tensor, residual' and the broadcast dout of the backward never exist.  Kept for the
+    backward: x0 and residual themselves (no copies), mean / rstd per row and the seed."""
+
+    @staticmethod
+    def forward(ctx, x0, residual, weight, bias, eps, lengths, mode, dropout_p=0.0, seed=None):
+        x3 = x0.contiguous()
+        r3 = None if residual is None else residual.to(torch.float32).contiguous()
+        w = weight.detach().to(torch.float32).contiguous()
+        b = bias.detach().to(torch.float32).contiguous()
+        pooled, mean, rstd = _lib.add_norm_pool_fwd(x3, r3, w, b, eps, lengths=lengths, mode=mode, dropout_p=dropout_p, seed=seed)
+        ctx.save_for_backward(x3, r3, w, mean, rstd, lengths)
+        ctx.drop = (float(dropout_p), seed)
+        ctx.meta = (mode, None if residual is None else residual.dtype, weight.dtype, bias.dtype)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g):
+        x3, r3, w, mean, rstd, lengths = ctx.saved_tensors
+        mode, r_dtype, w_dtype, b_dtype = ctx.meta
+        dx, dres, dw, db = _lib.add_norm_pool_bwd(g.to(torch.float32).contiguous(), x3, r3, w, mean, rstd, lengths=lengths, mode=mode,
+                                                  need_dres=r_dtype is not None, dropout_p=ctx.drop[0], seed=ctx.drop[1])
+        return (dx.view(x3.shape), None if dres is None else dres.view(x3.shape).to(r_dtype), dw.to(w_dtype), db.to(b_dtype),
+                None, None, None, None, None)
+
+
+def dropout_add_layer_norm_pool(x0, residual, weight, bias, dropout_p, epsilon, lengths=None, mode="mean", residual_in_fp32=True):
+    """The pooled readout of a sequence classifier over the backbone's final norm (src/tasks/decoders.py SequenceDecoder, mode pool / sum,
+    restricted to one output position): ``(B, D)`` fp32
+
+        scale_b * sum_{t < n_b} LayerNorm(dropout(x0) + residual)[b, t]        scale_b = 1 / n_b ("mean") or 1 ("sum")
+
+    with ``n_b = lengths[b]`` clamped to [0, L] (``lengths``: (B,) integers on x0's device; None: L).  ``n_b = 0`` gives zeros.  One fused pass
+    where ``dropout_add_layer_norm`` has one (``residual_in_fp32``, D a multiple of 64 up to 1024, fp32 / bf16 / fp16); other shapes take the same
+    graph in PyTorch ops on the same device (fp32 LayerNorm, masked fp32 sum).  Host tensors are refused."""
+    if mode not in ("mean", "sum"):
+        raise ValueError(f"mode has to be 'mean' or 'sum', got {mode!r}")
+    if x0.dim() != 3:
+        raise ValueError(f"x0 has to be (B, L, D), got {tuple(x0.shape)}")
+    B, L, D = x0.shape
+    if lengths is not None:
+        if lengths.shape != (B,) or lengths.dtype.is_floating_point or lengths.device != x0.device:
+            raise ValueError("lengths has to be a (B,) integer tensor on x0's device")
+    if dropout_p > 0.0 and not dropout_p < 1.0:
+        raise ValueError(f"dropout probability has to be in [0, 1), got {dropout_p}")
+    if residual_in_fp32 and _fused_ok(x0, residual, weight) and _lib.add_norm_pool_supported(D, x0.dtype):
+        n32 = None if lengths is None else lengths.to(torch.int32).contiguous()
+        if dropout_p > 0.0:
+            seed = torch.empty(1, dtype=torch.int64, device=x0.device).random_()
+            return AddNormPoolFunc.apply(x0, residual, weight, bias, epsilon, n32, mode, float(dropout_p), seed)
+        return AddNormPoolFunc.apply(x0, residual, weight, bias, epsilon, n32, mode)
+    if dropout_p > 0.0:
+        x0 = F.dropout(x0, dropout_p, training=True)
+    res = x0 + residual if residual is not None else x0
+    out = F.layer_norm(res.to(torch.float32), (D,), None if weight is None else weight.float(), None if bias is None else bias.float(), epsilon)
+    return masked_pool(out, lengths, mode)
+
+
+def masked_pool(x, lengths=None, mode="mean"):
+    """(B, L, D) -> (B, D) fp32: the sum (``mode="sum"``) or mean of the first n_b = clamp(lengths[b], 0, L) positions in fp32 (None: all L);
+    n_b = 0 gives zeros"""
+    B, L, D = x.shape
+    x = x.to(torch.float32)
+    if lengths is None:
+        s = x.sum(1)
+        return s / L if mode == "mean" and L > 0 else s
+    n = lengths.to(device=x.device).clamp(0, L)
+    keep = torch.arange(L, device=x.device).unsqueeze(0) < n.unsqueeze(1)
+    s = (x * keep.unsqueeze(-1)).sum(1)
+    if mode == "mean":
+        s = s / n.clamp_min(1).to(torch.float32).unsqueeze(1)
+    return s

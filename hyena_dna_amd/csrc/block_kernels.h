@@ -247,4 +247,210 @@ __global__ void __launch_bounds__(BLK_THREADS) add_norm_bwd_kernel(AddNormArgs a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The pooled readout of a sequence classifier (src/tasks/decoders.py SequenceDecoder, mode pool / sum, on top of the backbone's
+// final norm, long_conv_lm.py:381-396):
+//     pooled[b, :] = scale_b * sum_{t < n_b} LayerNorm(dropout(x0[b, t]) + residual[b, t])        scale_b = 1 / n_b (mean) or 1 (sum)
+// inside the add + LayerNorm pass: neither the normalised (B, L, D) tensor nor residual' is written, and the backward needs no
+// (B, L, D) dout -- every row's dout is the one vector scale_b * g[b], held in registers.  Same arithmetic and layout as
+// add_norm_fwd_kernel (a wavefront owns a row, lane l the E channels from l E on).  The grid is (row chunks, B) and depends on
+// (B, L) only: n_b is read from device memory (`lengths`, int32, clamped to [0, L]; null: L), so one captured graph serves every
+// batch.  Sums are taken in a fixed order -- a wavefront over its rows, the 4 wavefronts through LDS, the chunks by
+// add_norm_pool_finish_kernel -- no atomics: bit-reproducible.
+// ---------------------------------------------------------------------------------------------------------------
+enum { POOL_MEAN = 0, POOL_SUM = 1 };
+
+struct AddNormPoolArgs {
+    const void* x;          // (B, L, D) elements of XDT: x0
+    const float* res_in;    // (B, L, D) fp32 or null: residual
+    const float* weight;    // (D,)
+    const float* bias;      // (D,)  fwd only
+    const int* lengths;     // (B,) device int32 or null
+    const float* g;         // bwd: (B, D) gradient of pooled
+    float* pooled;          // fwd: (B, D)
+    void* dx;               // bwd: (B, L, D) elements of XDT
+    float* dres;            // bwd: (B, L, D) fp32 or null
+    float* mean;            // (B L,)  fwd: out (rows t < n_b), bwd: in
+    float* rstd;            // (B L,)
+    float* part;            // fwd: [B][chunks][D]; bwd: [B * chunks][np][D] (dweight | dbias [| column sums of dx0 as stored])
+    int np;
+    int mode;               // POOL_MEAN / POOL_SUM
+    long L;
+    int D;
+    int chunk_rows;         // rows of a chunk: a multiple of BLK_WAVES
+    float eps;
+    const unsigned long long* seed;
+    unsigned drop_below;
+    float keep_scale;
+};
+
+__device__ __forceinline__ long pool_len(const AddNormPoolArgs& a, int b) {
+    if (a.lengths == nullptr) return a.L;
+    const long n = a.lengths[b];
+    return n < 0 ? 0 : (n > a.L ? a.L : n);
+}
+
+// residual' of one row in registers: dropout(x0) + residual, as add_norm_fwd_kernel forms it
+template <int XDT, int E>
+__device__ __forceinline__ void pool_row(const AddNormPoolArgs& a, size_t off, unsigned long long seed, float (&r)[E]) {
+    blk_load<XDT, E>(a.x, off, r);
+    if (a.seed != nullptr) blk_dropout<E>(r, off, seed, a.drop_below, a.keep_scale);
+    if (a.res_in != nullptr) {
+        float q[E];
+        blk_load<DT_F32, E>(a.res_in, off, q);
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) r[e] += q[e];
+    }
+}
+
+template <int XDT, int E>
+__global__ void __launch_bounds__(BLK_THREADS) add_norm_pool_fwd_kernel(AddNormPoolArgs a) {
+    HY_SMEM(smem);
+    HY_LDS float* red = HY_LDS_CAST(float, smem);            // [BLK_WAVES][64 * E]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = lane * E, D = 64 * E;
+    const int b = blockIdx.y;
+    const long n = pool_len(a, b);
+    const long t0 = (long)blockIdx.x * a.chunk_rows;
+    if (t0 >= n) return;                                     // a chunk of pad rows only: nothing is read, the finish kernel does not look at its slot
+    const long t1 = t0 + a.chunk_rows < n ? t0 + a.chunk_rows : n;
+    float w[E], bs[E], acc[E];
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) { w[e] = a.weight[c0 + e]; bs[e] = a.bias[c0 + e]; acc[e] = 0.f; }
+    const float inv_d = 1.f / (float)D;
+    const unsigned long long seed = a.seed != nullptr ? *a.seed : 0ull;
+    for (long t = t0 + wave; t < t1; t += BLK_WAVES) {
+        const long row = (long)b * a.L + t;
+        float r[E];
+        pool_row<XDT, E>(a, (size_t)row * D + c0, seed, r);
+        float s = 0.f;
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) s += r[e];
+        const float mean = wave_sum(s) * inv_d;
+        float v = 0.f;
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) v += (r[e] - mean) * (r[e] - mean);
+        const float rstd = 1.f / sqrtf(wave_sum(v) * inv_d + a.eps);
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) acc[e] += (r[e] - mean) * rstd * w[e] + bs[e];     // fp32, never rounded to the I/O type
+        if (lane == 0) { a.mean[row] = mean; a.rstd[row] = rstd; }
+    }
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) red[wave * D + c0 + e] = acc[e];
+    __syncthreads();
+    for (int i = threadIdx.x; i < D; i += BLK_THREADS) {
+        float s = 0.f;
+        HY_UNROLL
+        for (int q = 0; q < BLK_WAVES; ++q) s += red[q * D + i];                       // the 4 wavefronts, in order
+        a.part[((size_t)b * gridDim.x + blockIdx.x) * D + i] = s;
+    }
+}
+
+// pooled[b][j] = scale_b * sum over the chunks that hold rows < n_b, in index order: a workgroup owns 16 channels of one sequence, its 16
+// thread rows sum interleaved slices of the chunks (independent loads in flight), thread row 0 adds the slices in order.  (A template only
+// because this header is part of several translation units.)
+template <int S = 16>
+__global__ void __launch_bounds__(256) add_norm_pool_finish_kernel(AddNormPoolArgs a, int chunks) {
+    HY_SMEM(smem);
+    HY_LDS float* sm = HY_LDS_CAST(float, smem);             // [16][16]
+    const int jj = threadIdx.x & 15, cs = threadIdx.x >> 4;
+    const int b = blockIdx.y, D = a.D;
+    const int j = blockIdx.x * 16 + jj;
+    const int jc = j < D ? j : D - 1;
+    const long n = pool_len(a, b);
+    const int active = (int)((n + a.chunk_rows - 1) / a.chunk_rows);                   // <= chunks
+    const float* part = a.part + (size_t)b * chunks * D;
+    float s = 0.f;
+    int c = cs;
+    for (; c + 7 * 16 < active; c += 8 * 16) {
+        float v[8];
+        HY_UNROLL
+        for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(c + u * 16) * D + jc];
+        HY_UNROLL
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; c < active; c += 16) s += part[(size_t)c * D + jc];
+    sm[cs * 16 + jj] = s;
+    __syncthreads();
+    if (cs == 0 && j < D) {
+        float r = 0.f;
+        for (int q = 0; q < 16; ++q) r += sm[q * 16 + jj];
+        if (a.mode == POOL_MEAN) r = n > 0 ? r / (float)n : 0.f;                       // n_b = 0: zeros, never NaN
+        a.pooled[(size_t)b * D + j] = r;
+    }
+}
+
+// The backward.  dout of every row t < n_b is gv = scale_b g[b]: with it s1 = mean(gv w) is one number per sequence, dweight = gv * (sum of
+// the rows' xhat) and dbias = gv * (number of rows), so a row costs one butterfly (s2) instead of two.  residual' is rebuilt from x0 and
+// residual (dropout regenerated from the seed); rows t >= n_b get zeros without a load.
+template <int XDT, int E>
+__global__ void __launch_bounds__(BLK_THREADS) add_norm_pool_bwd_kernel(AddNormPoolArgs a) {
+    HY_SMEM(smem);
+    HY_LDS float* red = HY_LDS_CAST(float, smem);            // [BLK_WAVES][np][64 * E]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = lane * E, D = 64 * E, np = a.np;
+    const int b = blockIdx.y;
+    const long n = pool_len(a, b);
+    const long t0 = (long)blockIdx.x * a.chunk_rows;
+    const long t1 = t0 + a.chunk_rows < a.L ? t0 + a.chunk_rows : a.L;
+    const float scale = a.mode == POOL_MEAN ? (n > 0 ? 1.f / (float)n : 0.f) : 1.f;
+    const float inv_d = 1.f / (float)D;
+    float gv[E], gw[E], sxh[E], dxs[E], zero[E];
+    float s1 = 0.f, cnt = 0.f;
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) {
+        gv[e] = scale * a.g[(size_t)b * D + c0 + e];
+        gw[e] = gv[e] * a.weight[c0 + e];
+        s1 += gw[e];
+        sxh[e] = 0.f; dxs[e] = 0.f; zero[e] = 0.f;
+    }
+    s1 = wave_sum(s1) * inv_d;
+    const unsigned long long seed = a.seed != nullptr ? *a.seed : 0ull;
+    for (long t = t0 + wave; t < t1; t += BLK_WAVES) {
+        const long row = (long)b * a.L + t;
+        const size_t off = (size_t)row * D + c0;
+        if (t >= n) {                                        // a pad row (wave-uniform): its gradients are zero
+            blk_store<XDT, E>(a.dx, off, zero);
+            if (a.dres != nullptr) blk_store<DT_F32, E>(a.dres, off, zero);
+            continue;
+        }
+        float r[E];
+        pool_row<XDT, E>(a, off, seed, r);
+        const float mean = a.mean[row], rstd = a.rstd[row];
+        float s2 = 0.f, xh[E];
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) {
+            xh[e] = (r[e] - mean) * rstd;
+            s2 += gw[e] * xh[e];
+            sxh[e] += xh[e];
+        }
+        cnt += 1.f;
+        s2 = wave_sum(s2) * inv_d;
+        float dr[E];
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) dr[e] = rstd * (gw[e] - s1 - xh[e] * s2);
+        if (a.dres != nullptr) blk_store<DT_F32, E>(a.dres, off, dr);
+        if (a.seed != nullptr) blk_dropout<E>(dr, off, seed, a.drop_below, a.keep_scale);      // d x0 = d residual' through the same mask
+        blk_store<XDT, E>(a.dx, off, dr);
+        if (np == 3) {
+            HY_UNROLL
+            for (int e = 0; e < E; ++e) dxs[e] += Elem<XDT>::dec(Elem<XDT>::cvt(dr[e]));
+        }
+    }
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) {
+        red[(wave * np + 0) * D + c0 + e] = gv[e] * sxh[e];
+        red[(wave * np + 1) * D + c0 + e] = gv[e] * cnt;
+        if (np == 3) red[(wave * np + 2) * D + c0 + e] = dxs[e];
+    }
+    __syncthreads();
+    const size_t slot = (size_t)b * gridDim.x + blockIdx.x;
+    for (int i = threadIdx.x; i < np * D; i += BLK_THREADS) {
+        float s = 0.f;
+        HY_UNROLL
+        for (int q = 0; q < BLK_WAVES; ++q) s += red[q * np * D + i];
+        a.part[slot * np * D + i] = s;
+    }
+}
+
 }  // namespace hyena

@@ -1034,3 +1034,111 @@ int hyena_dropout_add_norm_bwd_colsum(const void* dout, int dout_dtype, const fl
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------
+// add + LayerNorm + pooled readout (include/hyena_block.h, hyena_add_norm_pool_*)
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+// rows of a chunk: a function of (B, L) only -- at most BLK_MAX_GRID workgroups over the batch, a multiple of BLK_WAVES rows each
+int pool_chunk_rows(int B, long L) {
+    long cap = BLK_MAX_GRID / B;
+    if (cap < 1) cap = 1;
+    long rows = (L + cap - 1) / cap;
+    rows = (rows + BLK_WAVES - 1) / BLK_WAVES * BLK_WAVES;
+    return (int)rows;
+}
+int pool_chunks(int B, long L) {
+    const int cr = pool_chunk_rows(B, L);
+    return (int)((L + cr - 1) / cr);
+}
+bool pool_shape_ok(int B, long L, int D) { return B >= 1 && B <= 65535 && L >= 1 && L <= HYENA_MAX_L && D >= 64; }
+
+template <int XDT>
+int pool_launch(bool fwd, const AddNormPoolArgs& a, int B, void* stream) {
+    const dim3 grid(pool_chunks(B, a.L), B);
+#define HY_POOL_CASE(e)                                                                                                   \
+    case e:                                                                                                               \
+        if (fwd) HY_LAUNCH((add_norm_pool_fwd_kernel<XDT, e>), grid, dim3(BLK_THREADS),                                   \
+                           (size_t)BLK_WAVES * 64 * e * sizeof(float), stream, a);                                        \
+        else HY_LAUNCH((add_norm_pool_bwd_kernel<XDT, e>), grid, dim3(BLK_THREADS),                                       \
+                       (size_t)BLK_WAVES * 3 * 64 * e * sizeof(float), stream, a);                                        \
+        break;
+    switch (a.D / 64) {
+        HY_POOL_CASE(1)
+        HY_POOL_CASE(2)
+        HY_POOL_CASE(4)
+        HY_POOL_CASE(8)
+        HY_POOL_CASE(16)
+        default: return HYENA_ERR_BAD_ARG;
+    }
+#undef HY_POOL_CASE
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+int pool_launch_dt(bool fwd, int xdt, const AddNormPoolArgs& a, int B, void* stream) {
+    switch (xdt) {
+        case HYENA_F32: return pool_launch<DT_F32>(fwd, a, B, stream);
+        case HYENA_BF16: return pool_launch<DT_BF16>(fwd, a, B, stream);
+        default: return pool_launch<DT_F16>(fwd, a, B, stream);
+    }
+}
+// the dropout fields of AddNormPoolArgs, by the rule of blk_set_dropout
+bool pool_set_dropout(AddNormPoolArgs& a, float p, const unsigned long long* seed) {
+    AddNormArgs t;
+    if (!blk_set_dropout(t, p, seed)) return false;
+    a.seed = t.seed; a.drop_below = t.drop_below; a.keep_scale = t.keep_scale;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int hyena_add_norm_pool_supported(int D, int x_dtype) { return hyena_add_norm_supported(D, x_dtype, x_dtype); }
+
+size_t hyena_add_norm_pool_partial_floats(int B, long L, int D) {
+    if (!pool_shape_ok(B, L, D)) return 0;
+    return (size_t)B * pool_chunks(B, L) * 3 * D;   // the backward's (dweight | dbias | column sums of dx0) per workgroup; the forward uses a third
+}
+
+int hyena_add_norm_pool_fwd(const void* x0, int x_dtype, const float* residual_in, const float* weight, const float* bias, float eps,
+                            float dropout_p, const unsigned long long* seed, const int* lengths, int mode, float* pooled, float* mean,
+                            float* rstd, float* partial, int B, long L, int D, void* stream) {
+    if (x0 == nullptr || weight == nullptr || bias == nullptr || pooled == nullptr || mean == nullptr || rstd == nullptr ||
+        partial == nullptr || (mode != POOL_MEAN && mode != POOL_SUM) || !pool_shape_ok(B, L, D) ||
+        !hyena_add_norm_pool_supported(D, x_dtype))
+        return HYENA_ERR_BAD_ARG;
+    AddNormPoolArgs a;
+    a.x = x0; a.res_in = residual_in; a.weight = weight; a.bias = bias; a.lengths = lengths; a.g = nullptr; a.pooled = pooled;
+    a.dx = nullptr; a.dres = nullptr; a.mean = mean; a.rstd = rstd; a.part = partial; a.np = 1; a.mode = mode; a.L = L; a.D = D;
+    a.chunk_rows = pool_chunk_rows(B, L); a.eps = eps;
+    if (!pool_set_dropout(a, dropout_p, seed)) return HYENA_ERR_BAD_ARG;
+    const int st = pool_launch_dt(true, x_dtype, a, B, stream);
+    if (st) return st;
+    HY_LAUNCH((add_norm_pool_finish_kernel<16>), dim3((D + 15) / 16, B), dim3(256), (size_t)256 * sizeof(float), stream, a, pool_chunks(B, L));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_add_norm_pool_bwd(const float* g, const void* x0, int x_dtype, const float* residual_in, const float* weight, const float* mean,
+                            const float* rstd, float dropout_p, const unsigned long long* seed, const int* lengths, int mode, void* dx0,
+                            float* d_residual_in, float* dweight, float* dbias, float* dx0_colsum, float* partial, int B, long L, int D,
+                            void* stream) {
+    if (g == nullptr || x0 == nullptr || weight == nullptr || mean == nullptr || rstd == nullptr || dx0 == nullptr || dweight == nullptr ||
+        dbias == nullptr || partial == nullptr || (mode != POOL_MEAN && mode != POOL_SUM) || !pool_shape_ok(B, L, D) ||
+        !hyena_add_norm_pool_supported(D, x_dtype))
+        return HYENA_ERR_BAD_ARG;
+    AddNormPoolArgs a;
+    a.x = x0; a.res_in = residual_in; a.weight = weight; a.bias = nullptr; a.lengths = lengths; a.g = g; a.pooled = nullptr;
+    a.dx = dx0; a.dres = d_residual_in; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd); a.part = partial;
+    a.np = dx0_colsum != nullptr ? 3 : 2; a.mode = mode; a.L = L; a.D = D; a.chunk_rows = pool_chunk_rows(B, L); a.eps = 0.f;
+    if (!pool_set_dropout(a, dropout_p, seed)) return HYENA_ERR_BAD_ARG;
+    const int st = pool_launch_dt(false, x_dtype, a, B, stream);
+    if (st) return st;
+    const int slots = B * pool_chunks(B, L);
+    RedBatch red;                                   // every workgroup wrote its slot (zeros where it held pad rows only): fixed order
+    red.add(partial, dweight, slots, D, a.np * D, 0);
+    red.add(partial + D, dbias, slots, D, a.np * D, 0);
+    if (dx0_colsum != nullptr) red.add(partial + 2 * D, dx0_colsum, slots, D, a.np * D, 0);
+    HY_LAUNCH(filter_reduce_multi_kernel, dim3(red.blocks()), dim3(256), FLT_RED_SMEM, stream, red.jobs);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+}  // extern "C"

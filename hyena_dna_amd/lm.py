@@ -500,6 +500,11 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         self.lm_head.weight = self.backbone.embeddings.word_embeddings.weight
 
     def hidden(self, input_ids, position_ids=None, inference_params=None):
+        return self._final_norm(*self.trunk(input_ids, position_ids, inference_params=inference_params))
+
+    def trunk(self, input_ids, position_ids=None, inference_params=None):
+        """(hidden_states, residual) as the last block leaves them, in front of drop_f / ln_f (long_conv_lm.py:367-380): what a readout that
+        carries the final norm inside its own pass starts from (classifier.HyenaDNAClassifier)"""
         bb = self.backbone
         emb, blk0 = bb.embeddings, bb.layers[0]
         # inference_params reach every mixer through the block's mixer_kwargs (long_conv_lm.py:375-378); a non-empty mixer_kwargs also keeps the
@@ -523,6 +528,11 @@ class HyenaDNALM(nn.Module, GenerationMixin):
             rest = bb.layers
         for blk in rest:
             hidden_states, residual = blk(hidden_states, residual, mixer_kwargs=mk())
+        return hidden_states, residual
+
+    def _final_norm(self, hidden_states, residual):
+        """drop_f -> add -> ln_f (long_conv_lm.py:381-396)"""
+        bb = self.backbone
         if self.fused_dropout_add_ln:
             return dropout_add_layer_norm(hidden_states, residual, bb.ln_f.weight, bb.ln_f.bias,
                                           bb.drop_f.p if self.training else 0.0, bb.ln_f.eps, prenorm=False,

@@ -11,7 +11,8 @@ of which exist in this image) reduced to what the hot path needs to be trained:
   (``torch.cuda.mem_get_info``), same unit (MiB / 1000, rounded);
 * ``set_affinity`` -- src/callbacks/gpu_affinity.py binds the rank to the cores of its GPU's socket via NVML / libcudart; here: the
   NUMA node of the GPU's PCI device from sysfs -> ``os.sched_setaffinity`` (no-op where sysfs has no answer);
-* ``build_model`` -> ``hyena_dna_amd.lm.HyenaDNALM`` from the ``model:`` node;
+* ``build_model`` -> ``hyena_dna_amd.lm.HyenaDNALM`` from the ``model:`` node (``_name_: dna_embedding`` + the ``decoder:`` node ->
+  ``hyena_dna_amd.classifier.HyenaDNAClassifier``; ``make_synthetic_classification`` stands in for the GenomicBenchmarks downloads);
 * ``build_optimizer`` -- the parameter groups of ``SequenceLightningModule.configure_optimizers`` (train.py:443-468): all
   parameters without an ``_optim`` tag in the first group with the optimizer's hyperparameters, then one group per distinct
   ``_optim`` dict (the Hyena filter's ``lr`` / ``weight_decay = 0``, src/utils/train.py:142-156);
@@ -39,7 +40,7 @@ def _token_cross_entropy():
     return token_cross_entropy
 
 __all__ = ["compose", "compose_raw", "apply_overrides", "resolve", "gpu_mem_gb", "set_affinity", "build_model", "build_optimizer", "optimizer_groups",
-           "TimmCosineSchedule", "make_synthetic_genome", "train"]
+           "TimmCosineSchedule", "make_synthetic_genome", "make_synthetic_classification", "train"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -253,16 +254,35 @@ def set_affinity(local_rank):
 # model, optimizer, schedule
 # ---------------------------------------------------------------------------------------------------------------------
 def build_model(cfg):
-    """``model:`` node (``_name_: lm`` -> registry.model['lm'] = ConvLMHeadModel in the reference) -> HyenaDNALM."""
+    """``model:`` node -> the model.  ``_name_: lm`` (registry.model['lm'] = ConvLMHeadModel in the reference) -> HyenaDNALM;
+    ``_name_: dna_embedding`` (DNAEmbeddingModel) together with the ``decoder:`` node (``_name_: sequence``, ``mode``, ``l_output``; its
+    ``d_output`` is the dataset's, as the reference's task wiring passes it) -> classifier.HyenaDNAClassifier."""
     from .lm import HyenaDNALM
     m = dict(cfg["model"])
     name = m.pop("_name_", "lm")
-    if name != "lm":
-        raise NotImplementedError(f"model._name_={name!r}: this runner builds the hg38 language model ('lm') only")
+    if name not in ("lm", "dna_embedding"):
+        raise NotImplementedError(f"model._name_={name!r}: this runner builds the hg38 language model ('lm') and the sequence "
+                                  "classifier on its backbone ('dna_embedding') only")
     layer = dict(m.pop("layer"))
     if layer.get("_name_", "hyena") != "hyena":
         raise NotImplementedError(f"model.layer._name_={layer.get('_name_')!r}: Hyena mixers only")
-    return HyenaDNALM(layer=layer, **m)
+    if name == "lm":
+        return HyenaDNALM(layer=layer, **m)
+    from .classifier import DNAEmbeddingModel, HyenaDNAClassifier, SequenceDecoder
+    dec = cfg.get("decoder") or {"_name_": "sequence"}
+    dec = {"_name_": dec} if isinstance(dec, str) else dict(dec)
+    if dec.pop("_name_", "sequence") != "sequence":
+        raise NotImplementedError("decoder._name_: the sequence decoder only (token-level and N-d decoders are not part of this package)")
+    d_output = dec.pop("d_output", None)
+    if d_output is None:
+        d_output = (cfg.get("dataset") or {}).get("d_output")
+    backbone = DNAEmbeddingModel(layer=layer, **m)
+    # (the reference's SequenceLightningModule hands the decoder l_output = dataset.l_output, 0 for the sequence-level datasets: one squeezed row)
+    decoder = SequenceDecoder(backbone.d_output, d_output=d_output, l_output=dec.pop("l_output", 0), use_lengths=dec.pop("use_lengths", False),
+                              mode=dec.pop("mode", "last"))
+    if dec:
+        raise TypeError(f"decoder: unknown keys {sorted(dec)}")
+    return HyenaDNAClassifier(backbone, decoder)
 
 
 def optimizer_groups(named_params, opt_cfg):
@@ -375,6 +395,33 @@ def make_synthetic_genome(directory, n_chr=2, chr_len=400_000, n_intervals=64, i
             split = "train" if i % 8 < 6 else ("valid" if i % 8 == 6 else "test")
             f.write(f"chr{c}\t{start}\t{start + interval_len}\t{split}\n")
     return fasta, bed
+
+
+def make_synthetic_classification(n, max_length=256, min_length=None, motif="TATAAGGC", seed=0, pad_token_id=4, copies=1):
+    """A two-class toy set with the shape of the GenomicBenchmarks tasks (which need a download): fixed-seed random DNA of variable length, class 1
+    carries ``motif`` at ``copies`` random positions (they may overlap: at least one survives), class 0 does not (an accidental occurrence is broken up).  -> (ids (n, max_length) int64, END-padded
+    with ``pad_token_id``; lengths (n,) int64; labels (n,) int64), tokens as tokenizer.DNACharTokenizerLUT maps them (A C G T -> 7..10)."""
+    g = torch.Generator().manual_seed(seed)
+    min_length = max(len(motif), max_length // 2) if min_length is None else min_length
+    if not len(motif) <= min_length <= max_length:
+        raise ValueError("need len(motif) <= min_length <= max_length")
+    m = torch.tensor(["ACGT".index(c) for c in motif]) + 7
+    K = len(m)
+    lengths = torch.randint(min_length, max_length + 1, (n,), generator=g)
+    labels = torch.randint(0, 2, (n,), generator=g)
+    ids = torch.randint(7, 11, (n, max_length), generator=g)
+    for i in range(n):
+        Li = int(lengths[i])
+        row = ids[i]
+        win = row[:Li].unfold(0, K, 1) if Li >= K else None
+        if win is not None:                                        # no accidental motif in either class
+            for j in (win == m).all(1).nonzero().flatten().tolist():
+                row[j] = 7 + (int(m[0]) - 7 + 1) % 4
+        if labels[i] == 1:
+            for at in torch.randint(0, Li - K + 1, (copies,), generator=g).tolist():
+                row[at:at + K] = m
+        row[Li:] = pad_token_id
+    return ids, lengths, labels
 
 
 def build_dataset(cfg, split="train"):
