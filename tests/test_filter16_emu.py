@@ -1,11 +1,21 @@
 """The implicit filter under 16-bit autocast (include/hyena_filter.h: hyena_filter16_fwd / _bwd) on the CPU-emulated kernels vs the
 oracle's restatement of HyenaFilter.filter (hyena.py:229-238) evaluated under torch.autocast('cpu', dtype): the reference's own graph
 with its own roundings.  The kernels round where that graph rounds (csrc/filter16_kernels.h), so the filter itself is compared
-element-wise at fp32-accumulation noise, not at 16-bit tolerance."""
+element-wise at fp32-accumulation noise, not at 16-bit tolerance.
+
+And layer by layer on the kernels' own intermediates (tests/filter16_local.py): every saved pre-activation and every filter tap against
+an fp64 restatement of ITS layer evaluated at the kernel's previous pre-activation -- half a 16-bit ulp plus an fp32 accumulation bound
+per element, no amplification by sin(10 a) -- and every gradient against the fp64 backward of the same graph at the saved
+pre-activations, held to a quarter of what ignoring the 16-bit roundings of that graph costs.  The fp64 backward itself is pinned to the
+oracle's autocast graph, and the band in which the kernels' sine may round either way (tau) to the measured error of hy_sincos.  The
+same checks run on the gfx950 library in tests/test_gpu_filter.py; figures of both in profiles/filter16_local.md."""
+import ctypes
+
 import pytest
 import torch
 
 from oracle import hyena_oracle as O
+from tests import filter16_local as FL
 from tests.test_filter_emu import NAMES, _make_filter, _rel
 
 
@@ -132,3 +142,90 @@ def test_filter16_vs_reference_minted_autocast_vectors(emu_backend, golden_filte
         assert got is not None and got.shape == g.shape, n
         tol = 1e-3 if (n.endswith("freq") and bf) else 6e-3
         assert _rel(got, g) < tol, (n, _rel(got, g))
+
+
+BF, HF = torch.bfloat16, torch.float16
+LOCAL_CASES = [(64, 300, 5, BF), (128, 512, 5, BF), (64, 1000, 3, BF), (256, 77, 7, BF), (128, 1, 5, BF), (256, 516, 5, BF),
+               (64, 300, 5, HF), (128, 130, 5, HF), (64, 33, 1, BF)]
+
+
+def _local_case(D, L, emb_dim, seed, **kw):
+    """kernel arguments of a _make_filter module; emb_dim below HyenaFilter's minimum of 3 (or even): the first columns of a wider embedding"""
+    f = _make_filter(D, L, emb_dim=max(3, emb_dim | 1), seed=seed, **kw)
+    args, shift, modulate = FL.module_args(f, L)
+    return f, FL.with_emb_dim(args, emb_dim), shift, modulate
+
+
+@pytest.mark.parametrize("D,L,emb_dim,dtype", LOCAL_CASES)
+def test_filter16_layer_local_vs_fp64(emu_backend, D, L, emb_dim, dtype):
+    """forward and backward conditions of tests/filter16_local.py (check_local) on the emulated kernels: pre-activations and filter element
+    by element, exactness and ambiguity shares, pad columns, SAVE template, E_g < N_g / 4 for every gradient, bitwise determinism"""
+    _, args, shift, modulate = _local_case(D, L, emb_dim, seed=D + L)
+    dk = torch.randn(D, L, generator=torch.Generator().manual_seed(1))
+    FL.check_local(emu_backend, args, shift, modulate, dtype, dk, label=f"emu D={D} L={L} E={emb_dim} {dtype}")
+
+
+@pytest.mark.parametrize("kw", [{"modulate": False}, {"shift": 0.05}, {"lr_pos_emb": 0.0}])
+def test_filter16_layer_local_options(emu_backend, kw):
+    """the same conditions with the modulation off, a non-zero shift, and z as a buffer (no dz); the module's autograd path -- with and
+    without grad mode -- hands out the bits of the direct calls"""
+    D, L = 64, 130
+    f, args, shift, modulate = _local_case(D, L, 5, seed=7, **kw)
+    assert modulate == kw.get("modulate", True) and shift == kw.get("shift", 0.0)
+    need_dz = isinstance(f.pos_emb.z, torch.nn.Parameter) and f.pos_emb.z.requires_grad
+    assert need_dz == ("lr_pos_emb" not in kw)
+    dk = torch.randn(D, L, generator=torch.Generator().manual_seed(5))
+    res = FL.check_local(emu_backend, args, shift, modulate, BF, dk, need_dz=need_dz, label=f"emu options {kw}")
+    FL.check_module_path(f, L, BF, dk, res)
+
+
+@pytest.mark.parametrize("D,L,emb_dim", [(64, 300, 5), (128, 512, 5), (64, 1000, 3), (256, 77, 7), (128, 1, 5), (256, 516, 5)])
+def test_fp64_backward_reference_is_the_autocast_graph(monkeypatch, D, L, emb_dim):
+    """the fp64 backward of tests/filter16_local.py, independent of any kernel: fed the ORACLE'S pre-activations under torch.autocast('cpu', bf16),
+    its gradients are that graph's to the graph's own final rounding of the sums (the bounds of test_filter16_bf16_is_the_autocast_graph)"""
+    f = _make_filter(D, L, emb_dim=emb_dim, seed=D + L)
+    dk = torch.randn(D, L, generator=torch.Generator().manual_seed(1))
+    acts = []
+
+    class RecordingF:
+        @staticmethod
+        def linear(h, w, b=None):
+            out = torch.nn.functional.linear(h, w, b)
+            acts.append(out.detach())
+            return out
+    monkeypatch.setattr(O, "F", RecordingF)
+    _, sd = _oracle_autocast(f.state_dict(), L, torch.bfloat16, dk)
+    monkeypatch.undo()
+    assert len(acts) == 4 and all(a.dtype == torch.bfloat16 and a.shape == (1, L, 64) for a in acts[:3])
+    args, shift, modulate = FL.module_args(f, L)
+    g = FL.backward_ref(dk, [a[0].t() for a in acts[:3]], args, shift, modulate, torch.bfloat16, roundings=True)
+    for name, key in zip(NAMES, ("dz", "dw0", "db0", "dw1", "db1", "dw2", "db2", "dw3", "dfreq")):
+        ref = sd["filter_fn." + name].grad
+        if name.endswith("freq"):
+            ref = sum(sd[f"filter_fn.implicit_filter.{i}.freq"].grad for i in (1, 3, 5)).reshape(-1)
+        if key == "dz":
+            ref = ref[0, :L]
+            assert not ref.new_zeros(()).equal(ref.abs().sum())
+        tol = 1e-3 if key == "dfreq" else 6e-3
+        assert g[key].shape == ref.shape, (name, g[key].shape, ref.shape)
+        assert _rel(g[key], ref) < tol, (name, _rel(g[key], ref))
+
+
+def test_hy_sincos_error_is_covered_by_tau(emu_backend):
+    """hy_sincos (csrc/filter_kernels.h) states no error bound: measured here on the CPU build against fp64 over the argument range the
+    local checks allow (|freq a| <= SINCOS_RANGE, asserted there), the band tau in which the kernels' sine may round either way must be
+    at least 4 x its largest absolute error"""
+    lib = emu_backend.lib()
+    lib.hipemu_probe_sincos.restype = None
+    lib.hipemu_probe_sincos.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long]
+    X = FL.SINCOS_RANGE
+    g = torch.Generator().manual_seed(0)
+    x = torch.cat([torch.linspace(-X, X, (1 << 22) + 1, dtype=torch.float64).float(),
+                   (torch.rand(1 << 20, generator=g, dtype=torch.float64) * 2 - 1).mul(32).float(),      # where the test inputs live (|x| < 21)
+                   torch.tensor([0.0, -0.0, X, -X])]).contiguous()
+    sn, cs = torch.empty_like(x), torch.empty_like(x)
+    lib.hipemu_probe_sincos(x.data_ptr(), sn.data_ptr(), cs.data_ptr(), x.numel())
+    es = (sn.double() - torch.sin(x.double())).abs().max().item()
+    ec = (cs.double() - torch.cos(x.double())).abs().max().item()
+    print(f"[filter16-local] hy_sincos over |x| <= {X}: max abs error sin {es:.3g}, cos {ec:.3g}; tau = {FL.TAU:.3g}")
+    assert FL.TAU >= 4 * max(es, ec), (es, ec, FL.TAU)
