@@ -129,7 +129,8 @@ def test_mlp_kernels_vs_autocast_graph(emu_backend, P, K, N, dtype):
     d = (da.float() - da_ref.float()).abs()
     assert (d <= 2 * eps * da_ref.float().abs() + 2 * eps * 1e-2).all()           # (dh itself may differ by an ulp: another summation order)
     assert (da != da_ref).float().mean() < 0.03
-    assert ((db1 - da.float().sum(0)).abs() <= 1e-5 * (1 + da.float().abs().sum(0))).all()
+    from tests.proj_local import mlp_db1_bound
+    assert ((db1.double() - da.double().sum(0)).abs() <= mlp_db1_bound(da, P, N)).all()            # the derived bound of the fixed-order sum
 
 
 def test_fused_mlp_module_matches_the_unfused_graph(emu_backend, monkeypatch):
@@ -405,6 +406,7 @@ def test_out_proj_dgrad_with_the_gate_backward_in_its_epilogue(emu_backend, B, L
     tile above (L = 2500: three runs), sequences end inside tiles, pieces end inside pieces, rows are pitched."""
     _lib = emu_backend
     from hyena_dna_amd.projection import cm_from_pm
+    from tests import proj_local as PL
     for exact in (True, False):
         dy2, Wo, y, xT, bin_, w, b = _dgrad_operands(B, L, Lx, D, dtype, seed=L + D + exact, exact=exact)
         yp, xp = _lib.empty_rows((B, D), L, dtype, y.device), _lib.empty_cm(3 * D, B, Lx, dtype, y.device)
@@ -419,6 +421,9 @@ def test_out_proj_dgrad_with_the_gate_backward_in_its_epilogue(emu_backend, B, L
         assert _lib.ld_of(dyc) == _lib.ld_of(yp)
         assert (dx_f[D:] == 7.0).all() and (dx_f[:D, :, L:] == 7.0).all()              # only rows [0, D), positions < L are written
         red_f, red_u = part0[:, :, :5].sum(1), part[:D, :, :5].sum(1)
+        # each channel, each of the five sums, against its own derived bound (tests/proj_local.py)
+        S = PL.post_bwd_sum_scales(dzT, yp, xp, bin_, w, L)
+        assert ((red_f.double() - red_u.double()).abs() <= PL.dgrad_vs_cm_sums_bound(S, B, L, D, part.shape[1], dtype, exact)).all()
         if exact:
             assert torch.equal(dyc, dy_u) and torch.equal(dx_f[:D, :, :L], dx_u[:D, :, :L])
             assert (red_f - red_u).abs().max() <= 2e-5 * red_u.abs().max() + 1e-5
