@@ -1,5 +1,5 @@
-// launch.h -- kernel launch shim shared by the host translation units (fftconv.hip, onchip.hip): hipLaunchKernelGGL for
-// the product, tests/hipemu's CPU launcher with -DHIPEMU (tests only).
+// launch.h -- kernel launch shim shared by every host translation unit (the .hip files of this directory): hipLaunchKernelGGL
+// for the product, tests/hipemu's CPU launcher with -DHIPEMU (tests only).
 #pragma once
 #ifdef HIPEMU
 #include <tuple>

@@ -2,109 +2,68 @@
 #include "proj_kernels.h"
 #include "proj2_kernels.h"
 #include "launch.h"
+#include <type_traits>
 #include "../../include/hyena_fftconv.h"
 #include "../../include/hyena_proj.h"
 
 using namespace hyena;
 
 namespace {
-template <int K, int DT>
-int launch_inproj(const pj::InProjArgs& a, int grid, void* stream) {
-    typedef pj::IpCfg<K> C;
+// One launch of `Kernel` (the device marker of hy_allow_lds is per instantiation, i.e. per kernel).
+template <auto Kernel, class Args>
+int pj_launch(size_t lds, int threads, int grid, void* stream, const Args& a) {
     static thread_local int done = -1;
-    hy_allow_lds(pj::inproj_pre_fwd_kernel<K, DT>, C::LDS, &done);
-    HY_LAUNCH((pj::inproj_pre_fwd_kernel<K, DT>), dim3(grid), dim3(pj::PJ_THREADS), C::LDS, stream, a);
+    hy_allow_lds(Kernel, lds, &done);
+    HY_LAUNCH(Kernel, dim3(grid), dim3(threads), lds, stream, a);
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
-template <int K, int DT, int MODE>
-int launch_mlp(const pj::MlpArgs& a, int grid, void* stream) {
-    typedef pj::PmCfg<K> C;
-    static thread_local int done = -1;
-    hy_allow_lds(pj::mlp_kernel<K, DT, MODE>, C::lds(MODE), &done);
-    HY_LAUNCH((pj::mlp_kernel<K, DT, MODE>), dim3(grid), dim3(pj::PJ_THREADS), C::lds(MODE), stream, a);
-    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+// what every kernel family here is built for: d_model (the contraction length) 128 / 256, 16-bit operands
+bool pj_kd_ok(int K, int dtype) { return (K == 128 || K == 256) && (dtype == HYENA_BF16 || dtype == HYENA_F16); }
+// f(K, DT) with both as compile-time constants (std::integral_constant), for the pairs pj_kd_ok admits
+template <class F>
+int pj_dispatch(int K, int dtype, F f) {
+    typedef std::integral_constant<int, DT_BF16> BF;
+    typedef std::integral_constant<int, DT_F16> HF;
+    if (K == 256) return dtype == HYENA_BF16 ? f(std::integral_constant<int, 256>(), BF()) : f(std::integral_constant<int, 256>(), HF());
+    return dtype == HYENA_BF16 ? f(std::integral_constant<int, 128>(), BF()) : f(std::integral_constant<int, 128>(), HF());
 }
-// runs of tiles per unit group: a few per workgroup slot (2 per CU; tail balance), at least 8 tiles long (weight load amortised)
+// The schedule of every kernel here: each workgroup walks a run of consecutive tiles.  At most `cap` runs -- a few per resident workgroup slot balance
+// the tail --, of at least `min_run` tiles once there are that many (weight load and warm-up tile amortised): -> the runs, *tiles_per_wg their length
+int pj_runs(int tiles, int cap, int min_run, int* tiles_per_wg) {
+    const int runs = cap < tiles ? cap : tiles;
+    int len = (tiles + runs - 1) / runs;
+    if (len < min_run && tiles >= min_run) len = min_run;
+    *tiles_per_wg = len;
+    return (tiles + len - 1) / len;
+}
+// the grid of a kernel whose workgroups split the channels ncg ways: whole groups of 8 runs for each channel group
+int pj_grid(int runs, int ncg) { return ((runs + 7) / 8) * 8 * ncg; }
+
+// mlp_kernel: 2 workgroups per CU are resident; 8 workgroups per CU in all (the ncg unit groups of a run are workgroups of their own), runs of at least 8 tiles
 void mlp_schedule(size_t P, int ncg, pj::MlpArgs* a, int* runs_out, int* grid_out) {
     a->tiles = (int)((P + pj::PJ_NT - 1) / pj::PJ_NT);
-    int runs = 256 * 8 / ncg;
-    if (runs > a->tiles) runs = a->tiles;
-    a->tiles_per_wg = (a->tiles + runs - 1) / runs;
-    if (a->tiles_per_wg < 8 && a->tiles >= 8) a->tiles_per_wg = 8;
-    runs = (a->tiles + a->tiles_per_wg - 1) / a->tiles_per_wg;
-    *runs_out = runs;
-    *grid_out = ((runs + 7) / 8) * 8 * ncg;
+    *runs_out = pj_runs(a->tiles, 256 * 8 / ncg, 8, &a->tiles_per_wg);
+    *grid_out = pj_grid(*runs_out, ncg);
 }
-template <int K, int DT>
-int launch_outproj(const pj::OutProjArgs& a, int grid, void* stream) {
-    typedef pj::OpCfg<K> C;
-    if (a.ln_w != nullptr) {                       // the residual add + LayerNorm in the epilogue
-        static thread_local int done_ln = -1;
-        hy_allow_lds(pj::outproj_gate_fwd_kernel<K, DT, true>, C::LDS_LN, &done_ln);
-        HY_LAUNCH((pj::outproj_gate_fwd_kernel<K, DT, true>), dim3(grid), dim3(pj::PJ_THREADS), C::LDS_LN, stream, a);
-        return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-    }
-    static thread_local int done = -1;
-    hy_allow_lds(pj::outproj_gate_fwd_kernel<K, DT>, C::LDS, &done);
-    HY_LAUNCH((pj::outproj_gate_fwd_kernel<K, DT>), dim3(grid), dim3(pj::PJ_THREADS), C::LDS, stream, a);
-    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-}
-// generation 2 (proj2_kernels.h): K / 16 wavefronts per workgroup, operand rows prefetched a tile ahead, whole-row epilogue
-template <int K, int DT>
-int launch_outproj2(const pj::OutProjArgs& a, int grid, void* stream) {
-    typedef pj::Op2Cfg<K> C;
-    if (a.ln_w != nullptr) {
-        static thread_local int done_ln = -1;
-        hy_allow_lds(pj::outproj_gate_fwd2_kernel<K, DT, true>, C::LDS_LN, &done_ln);
-        HY_LAUNCH((pj::outproj_gate_fwd2_kernel<K, DT, true>), dim3(grid), dim3(C::THREADS), C::LDS_LN, stream, a);
-        return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-    }
-    static thread_local int done = -1;
-    hy_allow_lds(pj::outproj_gate_fwd2_kernel<K, DT, false>, C::LDS, &done);
-    HY_LAUNCH((pj::outproj_gate_fwd2_kernel<K, DT, false>), dim3(grid), dim3(C::THREADS), C::LDS, stream, a);
-    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-}
-template <int K, int DT>
-int launch_inproj2(const pj::InProjArgs& a, int grid, void* stream) {
-    typedef pj::Ip2Cfg<K> C;
-    static thread_local int done = -1;
-    hy_allow_lds(pj::inproj_pre_fwd2_kernel<K, DT>, C::LDS, &done);
-    HY_LAUNCH((pj::inproj_pre_fwd2_kernel<K, DT>), dim3(grid), dim3(pj::IP2_THREADS), C::LDS, stream, a);
-    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-}
-// which generation of a kernel family the entry points launch (hyena_proj_kernel_generation): A/B measurements and the tests of both
-int g_outproj_generation = 2;
-int g_inproj_generation = 1;        // generation 2 is built, parity-green and NOT faster at the long lengths (profiles/r6_inproj_gen2_not_kept.txt): selectable, not the default
-
-template <int K, int DT>
-int launch_dgrad(const pj::DgArgs& a, int grid, void* stream) {
-    typedef pj::DgCfg<K> C;
-    static thread_local int done = -1;
-    hy_allow_lds(pj::outproj_dgrad_gate_bwd_kernel<K, DT>, C::LDS, &done);
-    HY_LAUNCH((pj::outproj_dgrad_gate_bwd_kernel<K, DT>), dim3(grid), dim3(pj::PJ_THREADS), C::LDS, stream, a);
-    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
-}
-// runs of tiles per channel group of the dgrad kernel: a few per workgroup slot, at least 16 tiles long (weight load + the warm-up tile amortised)
+// ONE round of resident workgroups (DG_WGS per CU): a second, partly filled round costs up to half the launch (160 000 x 2: 640 workgroups
+// on 512 slots ran at 2.6 TB/s); runs of at least 16 tiles
 void dgrad_schedule(int B, int L, int D, pj::DgArgs* a, int* runs_out, int* grid_out) {
     const int ncg = D / (pj::PJ_WAVES * pj::DG_CB);
     a->tiles_per_seq = (L + pj::PJ_NT - 1) / pj::PJ_NT;
     a->tiles = B * a->tiles_per_seq;
-    // ONE round of resident workgroups (DG_WGS per CU): a second, partly filled round costs up to half the launch (160 000 x 2: 640 workgroups
-    // on 512 slots ran at 2.6 TB/s); runs of at least 16 tiles amortise the weight load and the warm-up tile
-    int runs = 256 * DG_WGS / ncg;
-    if (runs > a->tiles) runs = a->tiles;
-    a->tiles_per_wg = (a->tiles + runs - 1) / runs;
-    if (a->tiles_per_wg < 16 && a->tiles >= 16) a->tiles_per_wg = 16;
-    runs = (a->tiles + a->tiles_per_wg - 1) / a->tiles_per_wg;
-    a->nrec = runs;
-    *runs_out = runs;
-    *grid_out = ((runs + 7) / 8) * 8 * ncg;
+    a->nrec = *runs_out = pj_runs(a->tiles, 256 * DG_WGS / ncg, 16, &a->tiles_per_wg);
+    *grid_out = pj_grid(*runs_out, ncg);
 }
 template <int MODE>
 int dispatch_mlp(const pj::MlpArgs& a, int K, int dtype, int grid, void* stream) {
-    if (K == 256) return dtype == HYENA_BF16 ? launch_mlp<256, DT_BF16, MODE>(a, grid, stream) : launch_mlp<256, DT_F16, MODE>(a, grid, stream);
-    return dtype == HYENA_BF16 ? launch_mlp<128, DT_BF16, MODE>(a, grid, stream) : launch_mlp<128, DT_F16, MODE>(a, grid, stream);
+    return pj_dispatch(K, dtype, [&](auto k, auto dt) {
+        constexpr int KK = decltype(k)::value, DT = decltype(dt)::value;
+        return pj_launch<pj::mlp_kernel<KK, DT, MODE>>(pj::PmCfg<KK>::lds(MODE), pj::PJ_THREADS, grid, stream, a);
+    });
 }
+// which generation of a kernel family the entry points launch (hyena_proj_kernel_generation): A/B measurements and the tests of both
+int g_outproj_generation = 2;
+int g_inproj_generation = 1;        // generation 2 is built, parity-green and NOT faster at the long lengths (profiles/r6_inproj_gen2_not_kept.txt): selectable, not the default
 }  // namespace
 
 #if defined(PJ_PROFILE)
@@ -142,7 +101,7 @@ int hyena_colsum(const void* x, float* part, float* out, long P, int N, int dtyp
 }
 
 int hyena_mlp_supported(long P, int K, int N, int dtype) {
-    if (!(K == 128 || K == 256) || !(dtype == HYENA_BF16 || dtype == HYENA_F16)) return 0;
+    if (!pj_kd_ok(K, dtype)) return 0;
     if (N < 256 || N % 256 != 0 || P < 1) return 0;
     return (size_t)P < ((size_t)1 << 31) ? 1 : 0;
 }
@@ -187,7 +146,7 @@ int hyena_proj_kernel_generation(int family, int generation) {
 }
 
 int hyena_outproj_supported(int B, int L, int D, int dtype) {
-    if (!(D == 128 || D == 256) || !(dtype == HYENA_BF16 || dtype == HYENA_F16)) return 0;
+    if (!pj_kd_ok(D, dtype)) return 0;
     if (B < 1 || L < 64) return 0;                          // at least one whole 64-position tile per sequence
     return (size_t)B * (size_t)L < ((size_t)1 << 31) ? 1 : 0;
 }
@@ -222,29 +181,26 @@ int hyena_outproj_gate_addnorm_fwd_ld(const void* y, const void* xT, const float
     a.B = B; a.L = L; a.Lx = Lx; a.D = D; a.csx = csx; a.bsx = bsx; a.csz = csz; a.bsz = bsz; a.lda = lda;
     a.tiles_per_seq = (L + pj::PJ_NT - 1) / pj::PJ_NT;
     a.tiles = B * a.tiles_per_seq;
-    if (g_outproj_generation == 2) {
-        // one (d_model 256) or two (128) workgroups per CU are resident; a few runs per slot balance the tail, runs of >= 8 tiles amortise the
-        // weight load and the first tile's unhidden fetch
-        int runs2 = 256 * (D == 256 ? 4 : 8);
-        if (runs2 > a.tiles) runs2 = a.tiles;
-        a.tiles_per_wg = (a.tiles + runs2 - 1) / runs2;
-        if (a.tiles_per_wg < 8 && a.tiles >= 8) a.tiles_per_wg = 8;
-        runs2 = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-        if (D == 256) return dtype == HYENA_BF16 ? launch_outproj2<256, DT_BF16>(a, runs2, stream) : launch_outproj2<256, DT_F16>(a, runs2, stream);
-        return dtype == HYENA_BF16 ? launch_outproj2<128, DT_BF16>(a, runs2, stream) : launch_outproj2<128, DT_F16>(a, runs2, stream);
-    }
-    // generation 1: two workgroups per CU are resident; a few runs per slot balance the tail, runs of >= 8 tiles amortise the weight load
-    int runs = 256 * 8;
-    if (runs > a.tiles) runs = a.tiles;
-    a.tiles_per_wg = (a.tiles + runs - 1) / runs;
-    if (a.tiles_per_wg < 8 && a.tiles >= 8) a.tiles_per_wg = 8;
-    runs = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-    if (D == 256) return dtype == HYENA_BF16 ? launch_outproj<256, DT_BF16>(a, runs, stream) : launch_outproj<256, DT_F16>(a, runs, stream);
-    return dtype == HYENA_BF16 ? launch_outproj<128, DT_BF16>(a, runs, stream) : launch_outproj<128, DT_F16>(a, runs, stream);
+    // Generation 2 (proj2_kernels.h: K / 16 wavefronts per workgroup, operand rows prefetched a tile ahead, whole-row epilogue) keeps one workgroup
+    // per CU resident at d_model 256 and two at 128; generation 1 two.  4 runs per resident workgroup, at least 8 tiles long (these also amortise
+    // the first tile's unhidden fetch).
+    const bool gen2 = g_outproj_generation == 2;
+    const bool ln = ln_weight != nullptr;                   // the residual add + LayerNorm in the epilogue
+    const int runs = pj_runs(a.tiles, 256 * (gen2 && D == 256 ? 4 : 8), 8, &a.tiles_per_wg);
+    return pj_dispatch(D, dtype, [&](auto k, auto dt) {
+        constexpr int K = decltype(k)::value, DT = decltype(dt)::value;
+        typedef pj::Op2Cfg<K> C2;
+        typedef pj::OpCfg<K> C1;
+        if (gen2)
+            return ln ? pj_launch<pj::outproj_gate_fwd2_kernel<K, DT, true>>(C2::LDS_LN, C2::THREADS, runs, stream, a)
+                      : pj_launch<pj::outproj_gate_fwd2_kernel<K, DT, false>>(C2::LDS, C2::THREADS, runs, stream, a);
+        return ln ? pj_launch<pj::outproj_gate_fwd_kernel<K, DT, true>>(C1::LDS_LN, pj::PJ_THREADS, runs, stream, a)
+                  : pj_launch<pj::outproj_gate_fwd_kernel<K, DT, false>>(C1::LDS, pj::PJ_THREADS, runs, stream, a);
+    });
 }
 
 int hyena_outproj_dgrad_supported(int B, int L, int D, int dtype) {
-    if (!(D == 128 || D == 256) || !(dtype == HYENA_BF16 || dtype == HYENA_F16)) return 0;
+    if (!pj_kd_ok(D, dtype)) return 0;
     if (B < 1 || L < 1) return 0;
     return (size_t)B * (size_t)L < ((size_t)1 << 31) - 64 ? 1 : 0;
 }
@@ -268,12 +224,14 @@ int hyena_outproj_dgrad_gate_bwd_ld(const void* dy, const void* Wt, const void* 
     a.B = B; a.L = L; a.Lx = Lx; a.D = D; a.csx = csx; a.bsx = bsx; a.lda = lda;
     int runs, grid;
     dgrad_schedule(B, L, D, &a, &runs, &grid);
-    if (D == 256) return dtype == HYENA_BF16 ? launch_dgrad<256, DT_BF16>(a, grid, stream) : launch_dgrad<256, DT_F16>(a, grid, stream);
-    return dtype == HYENA_BF16 ? launch_dgrad<128, DT_BF16>(a, grid, stream) : launch_dgrad<128, DT_F16>(a, grid, stream);
+    return pj_dispatch(D, dtype, [&](auto k, auto dt) {
+        constexpr int K = decltype(k)::value, DT = decltype(dt)::value;
+        return pj_launch<pj::outproj_dgrad_gate_bwd_kernel<K, DT>>(pj::DgCfg<K>::LDS, pj::PJ_THREADS, grid, stream, a);
+    });
 }
 
 int hyena_proj_supported(int B, int Lx, int D, int dtype) {
-    if (!(D == 128 || D == 256) || !(dtype == HYENA_BF16 || dtype == HYENA_F16)) return 0;
+    if (!pj_kd_ok(D, dtype)) return 0;
     if (B < 1 || Lx < 8) return 0;
     return (size_t)B * (size_t)Lx < ((size_t)1 << 31) ? 1 : 0;
 }
@@ -293,34 +251,29 @@ int hyena_inproj_pre_fwd_ld(const void* u, const void* W, const float* bin, cons
     const size_t P = (size_t)B * Lx;
     a.tiles = (int)((P + pj::PJ_NT - 1) / pj::PJ_NT);
     if (g_inproj_generation == 2) {
-        // generation 2: one workgroup (12 wavefronts, 128 channels x 3 groups) per CU is resident; four per CU in total balance the tail, runs of
-        // >= 16 tiles amortise the weight load and the warm-up tile
-        const int ncg2 = D / pj::IP2_CH;
-        int runs2 = 256 * 4 / ncg2;
-        if (runs2 > a.tiles) runs2 = a.tiles;
-        a.tiles_per_wg = (a.tiles + runs2 - 1) / runs2;
-        if (a.tiles_per_wg < 16 && a.tiles >= 16) a.tiles_per_wg = 16;
-        runs2 = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-        const int grid2 = ((runs2 + 7) / 8) * 8 * ncg2;
-        if (D == 256) return dtype == HYENA_BF16 ? launch_inproj2<256, DT_BF16>(a, grid2, stream) : launch_inproj2<256, DT_F16>(a, grid2, stream);
-        return dtype == HYENA_BF16 ? launch_inproj2<128, DT_BF16>(a, grid2, stream) : launch_inproj2<128, DT_F16>(a, grid2, stream);
+        // generation 2: one workgroup (12 wavefronts, 128 channels x 3 groups) per CU is resident; 4 workgroups per CU in all, runs of at least 16 tiles
+        const int ncg = D / pj::IP2_CH;
+        const int grid = pj_grid(pj_runs(a.tiles, 256 * 4 / ncg, 16, &a.tiles_per_wg), ncg);
+        return pj_dispatch(D, dtype, [&](auto k, auto dt) {
+            constexpr int K = decltype(k)::value, DT = decltype(dt)::value;
+            return pj_launch<pj::inproj_pre_fwd2_kernel<K, DT>>(pj::Ip2Cfg<K>::LDS, pj::IP2_THREADS, grid, stream, a);
+        });
     }
-    // One workgroup per CU is resident (its wavefronts hold the weights in ~350 registers): a few runs per CU balance the tail,
-    // long runs amortise the weight load and the warm-up tile.
-    // Two workgroups per CU are resident (each wavefront holds its 48 weight rows in 96 registers): a few runs per slot balance
-    // the tail, long runs amortise the weight load and the warm-up tile.
+    // generation 1: two workgroups per CU are resident (__launch_bounds__(PJ_THREADS, 2): each wavefront holds its 48 weight rows in 96 registers);
+    // 8 workgroups per CU in all, runs of at least 8 tiles
     const int ncg = D / (pj::PJ_WAVES * pj::IP_CB);
-    int runs = 256 * 8 / ncg;
-    if (runs > a.tiles) runs = a.tiles;
-    a.tiles_per_wg = (a.tiles + runs - 1) / runs;
-    if (a.tiles_per_wg < 8 && a.tiles >= 8) a.tiles_per_wg = 8;
+    int runs = pj_runs(a.tiles, 256 * 8 / ncg, 8, &a.tiles_per_wg);
 #ifdef PJ_DBG_TPW
-    if (const char* e = getenv("HYENA_PJ_TPW")) a.tiles_per_wg = atoi(e);        // experiments only: run length override
+    if (const char* e = getenv("HYENA_PJ_TPW")) {         // experiments only: run length override
+        a.tiles_per_wg = atoi(e);
+        runs = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
+    }
 #endif
-    runs = (a.tiles + a.tiles_per_wg - 1) / a.tiles_per_wg;
-    const int grid = ((runs + 7) / 8) * 8 * ncg;
-    if (D == 256) return dtype == HYENA_BF16 ? launch_inproj<256, DT_BF16>(a, grid, stream) : launch_inproj<256, DT_F16>(a, grid, stream);
-    return dtype == HYENA_BF16 ? launch_inproj<128, DT_BF16>(a, grid, stream) : launch_inproj<128, DT_F16>(a, grid, stream);
+    const int grid = pj_grid(runs, ncg);
+    return pj_dispatch(D, dtype, [&](auto k, auto dt) {
+        constexpr int K = decltype(k)::value, DT = decltype(dt)::value;
+        return pj_launch<pj::inproj_pre_fwd_kernel<K, DT>>(pj::IpCfg<K>::LDS, pj::PJ_THREADS, grid, stream, a);
+    });
 }
 
 }  // extern "C"

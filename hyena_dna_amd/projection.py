@@ -116,22 +116,28 @@ def _use_merged(t, levels=None, rows=0):
     return levels is None or rows - (levels[0][0] + levels[0][1] * levels[0][2]) <= MERGE_MAX_ROWS
 
 
-def split_k_weight_grad(dy2, x2):
-    """dy2^T x2 (fp32) as batched position slices (split_plan) + the leftover rows, partial sums added in a fixed order (deterministic)."""
-    rows, n = dy2.shape
-    k = x2.shape[1]
-    levels, done = split_plan(rows, n * k)
-    merged = _use_merged(dy2, levels, rows)
+def _split_k(a_cn, b_nk, acc=None):
+    """acc + the sum over the positions p of a_cn[:, p] b_nk[p, :] in fp32, for views a_cn (C, n), b_nk (n, K) of any strides: batched position slices
+    (split_plan) + the leftover rows, the partial sums added to ``acc`` in a fixed order (deterministic).  The slices are VIEWS of the operands
+    (.view raises where one would need a copy: the layout decides which kernel the library picks)."""
+    C, n = a_cn.shape
+    K = b_nk.shape[1]
+    levels, done = split_plan(n, C * K)
+    merged = _use_merged(a_cn, levels, n)
     if merged:
         levels = levels[:1]
         done = levels[0][0] + levels[0][1] * levels[0][2]
-    dw = None
-    for p0, s, q in levels:
-        g = _bmm_f32(dy2[p0:p0 + s * q].view(s, q, n).transpose(1, 2), x2[p0:p0 + s * q].view(s, q, k)).sum(0)
-        dw = g if dw is None else dw + g
-    if done < rows:                                                 # the leftover rows
-        dw = dw + (_leftover_product(dy2.t(), x2, done) if merged else _tail_product(dy2.t(), x2, done))
-    return dw
+    for r0, s, q in levels:
+        g = _bmm_f32(a_cn[:, r0:r0 + s * q].view(C, s, q).permute(1, 0, 2), b_nk[r0:r0 + s * q].view(s, q, K)).sum(0)
+        acc = g if acc is None else acc + g
+    if done < n:                                                    # the leftover rows
+        acc = acc + (_leftover_product(a_cn, b_nk, done) if merged else _tail_product(a_cn, b_nk, done))
+    return acc
+
+
+def split_k_weight_grad(dy2, x2):
+    """dy2^T x2 (fp32) as batched position slices (split_plan) + the leftover rows, partial sums added in a fixed order (deterministic)."""
+    return _split_k(dy2.t(), x2)
 
 
 class SplitKLinearFunc(torch.autograd.Function):
@@ -232,41 +238,17 @@ def pm_from_cm(t, w, bias=None):
 def wgrad_cm_pm(d, x2):
     """sum over the positions of d[c, p] x2[p, k] -> (C, K) fp32 for d (C, B, L) packed or pitched rows and position-major x2 (B L, K): S batched
     position slices + a tail per piece, partial sums added in a fixed order (deterministic)"""
-    C, B, L = d.shape
-    k = x2.shape[1]
     total = None
-    for m, p0, n in _pieces(d, L):
-        xs = x2[p0:p0 + n]
-        levels, done = split_plan(n, C * k)
-        merged = _use_merged(d, levels, n)
-        if merged:
-            levels = levels[:1]
-            done = levels[0][0] + levels[0][1] * levels[0][2]
-        for r0, s, q in levels:
-            g = _bmm_f32(m[:, r0:r0 + s * q].reshape(C, s, q).permute(1, 0, 2), xs[r0:r0 + s * q].view(s, q, k)).sum(0)
-            total = g if total is None else total + g
-        if done < n:
-            total = total + (_leftover_product(m, xs, done) if merged else _tail_product(m, xs, done))
+    for m, p0, n in _pieces(d, d.shape[2]):
+        total = _split_k(m, x2[p0:p0 + n], total)                   # (ONE running sum across the pieces: fp32 addition is not associative)
     return total
 
 
 def wgrad_pm_cm(dy2, z):
     """sum over the positions of dy2[p, n] z[k, p] -> (N, K) fp32 for position-major dy2 (B L, N) and z (K, B, L) packed or pitched rows"""
-    K, B, L = z.shape
-    N = dy2.shape[1]
     total = None
-    for m, p0, n in _pieces(z, L):
-        ds = dy2[p0:p0 + n]
-        levels, done = split_plan(n, N * K)
-        merged = _use_merged(z, levels, n)
-        if merged:
-            levels = levels[:1]
-            done = levels[0][0] + levels[0][1] * levels[0][2]
-        for r0, s, q in levels:
-            g = _bmm_f32(ds[r0:r0 + s * q].view(s, q, N).transpose(1, 2), m[:, r0:r0 + s * q].reshape(K, s, q).permute(1, 2, 0)).sum(0)
-            total = g if total is None else total + g
-        if done < n:
-            total = total + (_leftover_product(ds.t(), m.t(), done) if merged else _tail_product(ds.t(), m.t(), done))
+    for m, p0, n in _pieces(z, z.shape[2]):
+        total = _split_k(dy2[p0:p0 + n].t(), m.t(), total)
     return total
 
 

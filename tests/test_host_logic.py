@@ -225,6 +225,126 @@ def test_leftover_rows_as_one_padded_batched_product(monkeypatch):
     assert torch.allclose(P._leftover_product(a, b, 4608), a[:, 4608:] @ b[4608:], rtol=1e-5, atol=1e-5) and P._leftover_product(a, b, 5000) is None
 
 
+def _expected_wgrad_products(P, kind, pieces, C, K, cs):
+    """The operand pairs projection._bmm_f32 must see for one weight gradient (C, K), in order, as (base tensor, shape, strides, element offset
+    from the base tensor): written out from split_plan.  ``pieces``: (offset of the piece inside the channel-major tensor, its first flattened
+    position, its positions); ``cs``: the channel-major tensor's row pitch.  kind "pm_pm" = split_k_weight_grad(dy2, x2), "cm_pm" = wgrad_cm_pm(d, x2),
+    "pm_cm" = wgrad_pm_cm(dy2, z); dy2 (rows, C) and x2 (rows, K) packed."""
+    def pm(name, W, p, s, q):                       # rows p .. p + s q of a packed (rows, W) matrix as s slices of (q, W)
+        return (name, (s, q, W), (q * W, W, 1), p * W)
+
+    def cm(name, W, o, s, q):                       # columns o .. o + s q of a (W, n) matrix of pitch cs as s slices of (W, q)
+        return (name, (s, W, q), (q, cs, 1), o)
+
+    def T(v):                                       # the slices transposed
+        return (v[0], (v[1][0], v[1][2], v[1][1]), (v[2][0], v[2][2], v[2][1]), v[3])
+
+    out = []
+    for o, p0, n in pieces:
+        def a_op(r, s, q):
+            return cm("d", C, o + r, s, q) if kind == "cm_pm" else T(pm("dy2", C, p0 + r, s, q))
+
+        def b_op(r, s, q):
+            return T(cm("z", K, o + r, s, q)) if kind == "pm_cm" else pm("x2", K, p0 + r, s, q)
+
+        levels, done = P.split_plan(n, C * K)
+        first = levels[0][1] * levels[0][2]
+        merged = P.MERGE_LEFTOVER and n - first <= P.MERGE_MAX_ROWS
+        if merged:
+            levels, done = levels[:1], first
+        out += [(a_op(r0, s, q), b_op(r0, s, q)) for r0, s, q in levels]
+        if done == n:
+            continue
+        if merged:                                  # the last w positions, the counted ones zeroed in a packed copy of a's
+            s2 = -(-(n - done) // 256)
+            w = 256 * s2
+            out.append((("copy", (s2, C, 256), (256, w, 1), 0), b_op(n - w, s2, 256)))
+        else:                                       # the last 256 positions as one slice: a's copy keeps the order of a's strides
+            a_copy = ("copy", (1, C, 256), (C * 256, 256, 1), 0) if kind == "cm_pm" else ("copy", (1, C, 256), (C, 1, C), 0)
+            out.append((a_copy, b_op(n - 256, 1, 256)))
+    return out
+
+
+def test_weight_gradient_operand_layouts_and_summation_order(monkeypatch):
+    """What the three weight gradients of projection.py hand the GEMM library -- every batched operand a VIEW of the caller's tensor with the strides
+    split_plan implies (the layout decides which library kernel runs), only the leftover's first operand a copy -- for packed, pitched and
+    per-sequence pitched channel-major tensors; row counts that divide evenly (16384), leave < 256 rows behind the first level (3 x 12001 = 36003;
+    12001) and have a second level and a tail (70001), with the leftover merged and split.  And the sums of several pieces are ONE running fp32
+    sum in piece order, not a sum of per-piece totals."""
+    import hyena_dna_amd.projection as P
+    from hyena_dna_amd import _lib
+    monkeypatch.setattr(P, "_MASKED_TAIL_ON_HOST", True)
+    real_bmm = P._bmm_f32
+    bases, calls = {}, []
+
+    def describe(t):
+        name, off = bases.get(t.untyped_storage().data_ptr(), ("copy", t.storage_offset()))
+        assert t.dtype == torch.bfloat16
+        return (name, tuple(t.shape), tuple(t.stride()), t.storage_offset() - off)
+
+    def recorder(a, b):
+        calls.append((describe(a), describe(b)))
+        return real_bmm(a, b)
+
+    monkeypatch.setattr(P, "_bmm_f32", recorder)
+    g = torch.Generator().manual_seed(3)
+    C, K = 3, 2
+    dev = torch.device("cpu")
+
+    def channel_major(W, B, L, layout):
+        if layout == "packed":
+            t = torch.empty(W, B, L, dtype=torch.bfloat16)
+        elif layout == "pitched":
+            t = _lib.empty_cm(W, B, L, torch.bfloat16, dev)
+        else:                                       # every sequence on a pitch of its own: no (W, B L) matrix view
+            bs = _lib.row_pitch(L) + 64
+            t = torch.as_strided(torch.empty(W * B * bs, dtype=torch.bfloat16), (W, B, L), (B * bs, bs, 1))
+        t.copy_(torch.randn(W, B, L, generator=g).to(torch.bfloat16))
+        return t
+
+    cases = [("packed", 1, 16384), ("packed", 3, 12001), ("pitched", 3, 12001), ("pitched", 1, 70001),
+             ("pieces", 2, 16384), ("pieces", 2, 12001), ("pieces", 2, 70001)]
+    assert len(P.split_plan(16384, C * K)[0]) == 1 and P.split_plan(16384, C * K)[1] == 16384
+    assert len(P.split_plan(36003, C * K)[0]) == 1 and 0 < 36003 - P.split_plan(36003, C * K)[1] < 256
+    assert len(P.split_plan(12001, C * K)[0]) == 1 and 0 < 12001 - P.split_plan(12001, C * K)[1] < 256
+    assert len(P.split_plan(70001, C * K)[0]) == 2 and 0 < 70001 - P.split_plan(70001, C * K)[1] < 256
+    for layout, B, L in cases:
+        rows = B * L
+        d, z = channel_major(C, B, L, layout), channel_major(K, B, L, layout)
+        x2 = torch.randn(rows, K, generator=g).to(torch.bfloat16)
+        dy2 = torch.randn(rows, C, generator=g).to(torch.bfloat16)
+        bases.clear()
+        bases.update({t.untyped_storage().data_ptr(): (name, t.storage_offset()) for name, t in (("d", d), ("z", z), ("x2", x2), ("dy2", dy2))})
+        cs, bs = _lib.cm_strides(d)
+        assert _lib.cm_strides(z) == (cs, bs) and (_lib.cm_matrix(d) is None) == (layout == "pieces")
+        assert (cs, bs) == {"packed": (rows, L), "pitched": (_lib.row_pitch(rows), L), "pieces": (B * (_lib.row_pitch(L) + 64), _lib.row_pitch(L) + 64)}[layout]
+        pieces = [(b * bs, b * L, L) for b in range(B)] if layout == "pieces" else [(0, 0, rows)]
+        for merged in (True, False):
+            monkeypatch.setattr(P, "MERGE_LEFTOVER", merged)
+            for kind, fn, args in (("pm_pm", P.split_k_weight_grad, (dy2, x2)), ("cm_pm", P.wgrad_cm_pm, (d, x2)), ("pm_cm", P.wgrad_pm_cm, (dy2, z))):
+                del calls[:]
+                got = fn(*args)
+                want = _expected_wgrad_products(P, kind, pieces if kind != "pm_pm" else [(0, 0, rows)], C, K, cs)
+                assert calls == want, (layout, B, L, merged, kind, calls, want)
+                assert got.dtype == torch.float32 and got.shape == (C, K)
+                if layout != "pieces" or kind == "pm_pm":
+                    continue
+                # several pieces: (((g1 + g2) + leftover) + g1') + ... with the products in the layouts asserted above
+                total = None
+                for b in range(B):
+                    a_cn = d[:, b, :] if kind == "cm_pm" else dy2[b * L:(b + 1) * L].t()
+                    b_nk = x2[b * L:(b + 1) * L] if kind == "cm_pm" else z[:, b, :].t()
+                    levels, done = P.split_plan(L, C * K)
+                    if merged:
+                        levels, done = levels[:1], levels[0][1] * levels[0][2]
+                    for r0, s, q in levels:
+                        part = real_bmm(a_cn[:, r0:r0 + s * q].unflatten(1, (s, q)).permute(1, 0, 2), b_nk[r0:r0 + s * q].unflatten(0, (s, q))).sum(0)
+                        total = part if total is None else total + part
+                    if done < L:
+                        total = total + (P._leftover_product if merged else P._tail_product)(a_cn, b_nk, done)
+                assert torch.equal(got, total), (layout, L, merged, kind)
+
+
 def test_split_k_linear_gradients_match_linear():
     """hyena_dna_amd/projection.py: the slice-batched weight gradient equals autograd's dy^T x (hyena.py:391,440)"""
     from hyena_dna_amd.projection import SplitKLinearFunc, split_count

@@ -45,6 +45,19 @@ def test_colsum(emu_backend, P, N, dtype):
     PL.run_colsum(emu_backend, DEV, dtype, P, N, seed=P + N, label="emu", path="")
 
 
+@pytest.mark.parametrize("B,L", [(1, 1 << 20), (1, (1 << 20) - 1), (8, 32767), (2, 159999), (1, 1000000)])
+def test_schedule_at_the_workload_sizes(emu_backend, B, L):
+    """the small cases above never reach the cap on runs (2^20 positions: 16384 tiles on 512 - 1024 runs): the partial buffers of mlp_kernel<1> and
+    the dgrad kernel at the workload's position counts against PL.schedule (size queries: nothing is launched)"""
+    lib = emu_backend.lib()
+    for N in (512, 1024):
+        runs, tpw = PL.mlp_schedule(B * L, N)
+        assert lib.hyena_mlp_partial_floats(B * L, N) == runs * N, (B, L, N)
+    for D in (128, 256):
+        runs, tpw = PL.dgrad_schedule(B, L, D)
+        assert lib.hyena_outproj_dgrad_partial_floats(B, L, D) == D * runs * 8, (B, L, D)
+
+
 def test_references_alone():
     """the references and bounds without any kernel: the GELU derivative is autograd's, its error model covers an fp32 evaluation of pm_gelu's
     operation order, and the operands drawn for the cases keep the bound of a product below its smallest term in fp16"""
