@@ -177,6 +177,9 @@ def lib():
         L.hyena_decode_conv.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
         L.hyena_decode_post.restype = c_int
         L.hyena_decode_post.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+        for rows, one in ((L.hyena_decode_pre_rows, L.hyena_decode_pre), (L.hyena_decode_conv_rows, L.hyena_decode_conv),
+                          (L.hyena_decode_post_rows, L.hyena_decode_post)):          # per-row positions: same arguments, pos -> B ints
+            rows.restype, rows.argtypes = c_int, one.argtypes
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -814,6 +817,47 @@ def decode_post(part, hist, fb, x0, z, pos, B, Lcap):
     with _backend.guard(z.device):
         check(lib().hyena_decode_post(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(), z.data_ptr(),
                                       pos.data_ptr(), int(B), D, int(Lcap), lda, dtype_code(hist.dtype), _backend.stream(z.device)))
+
+
+# ---- the same step with one position per row: pos a (>= B,) int32 device tensor, row b stands at pos[b]; rows outside [0, Lcap) are parked ----
+def _pos_rows(pos, B):
+    assert pos.dtype == torch.int32 and pos.dim() == 1 and pos.is_contiguous() and pos.shape[0] >= B
+
+
+def decode_pre_rows(x2, bin_, w, b, tail, hist, x0, pos, Lcap):
+    """decode_pre with t_b = pos[b]: hist[b, :, t_b] = v * x1 of row b, x0 (B, D) fp32, the tails of the rows that advance shifted"""
+    _require_gpu(x2, "x")
+    B, D3 = x2.shape
+    Bcap, D, lda = _hist(hist)
+    assert D3 == 3 * D and x2.stride(1) == 1 and hist.dtype == x2.dtype
+    _pos_rows(pos, B)
+    with _backend.guard(x2.device):
+        check(lib().hyena_decode_pre_rows(x2.data_ptr(), x2.stride(0), None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                          tail.data_ptr(), hist.data_ptr(), x0.data_ptr(), pos.data_ptr(), B, Bcap, D, int(Lcap), lda,
+                                          dtype_code(x2.dtype), _backend.stream(x2.device)))
+
+
+def decode_conv_rows(k, hist, part, pos, B, Lcap):
+    """part[chunk][b][d] = the chunk's share of sum_{s <= t_b} k[d, t_b - s] hist[b, d, s], written for the chunks that start at or below t_b"""
+    _require_gpu(k, "k")
+    _, D, lda = _hist(hist)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    _pos_rows(pos, B)
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv_rows(k.data_ptr(), k.stride(0), hist.data_ptr(), part.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap),
+                                           lda, dtype_code(hist.dtype), _backend.stream(k.device)))
+
+
+def decode_post_rows(part, hist, fb, x0, z, pos, B, Lcap):
+    """z[b] = round(round(sum of row b's partials + fb hist[b, :, t_b]) * x0[b]); advances every pos[b] inside [0, Lcap)"""
+    _require_gpu(z, "z")
+    _, D, lda = _hist(hist)
+    assert z.dtype == hist.dtype and z.is_contiguous()
+    _pos_rows(pos, B)
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post_rows(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
+                                           z.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap), lda, dtype_code(hist.dtype),
+                                           _backend.stream(z.device)))
 
 
 # ---- input projection on the matrix cores with the front of the shell in its epilogue (include/hyena_proj.h) --------------------

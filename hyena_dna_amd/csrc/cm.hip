@@ -184,4 +184,40 @@ int hyena_decode_post(const float* part, const void* vg, const float* fb, const 
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
+// ---- per-row positions: pos points at B ints, row b stands at pos[b] (same argument checks, same grids) ----------------------------------
+int hyena_decode_pre_rows(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vg, float* x0,
+                          const int* pos, int B, int Bcap, int D, int Lcap, int lda, int dtype, void* stream) {
+    if (x == nullptr || w == nullptr || b == nullptr || tail == nullptr || x0 == nullptr || pos == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) ||
+        Bcap < B || ldx < 3 * D || (long)Bcap * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.x = x; a.bin = bin; a.w = w; a.b = b; a.tail = tail; a.vg = vg; a.x0 = x0; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Bcap = Bcap; a.Lcap = Lcap; a.ldx = ldx; a.lda = lda;
+    HY_DEC_DISPATCH(decode_pre_rows_kernel, dim3((B * D + DEC_THREADS - 1) / DEC_THREADS), DEC_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_conv_rows(const float* k, int ldk, const void* vg, float* part, const int* pos, int B, int D, int Lcap, int lda, int dtype,
+                           void* stream) {
+    if (k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || pos == nullptr ||
+        !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || D > 65535)
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.k = k; a.vg = const_cast<void*>(vg); a.part = part; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_conv_rows_kernel, dim3(dec_chunks(Lcap), D), DEC_THREADS, (DEC_KLDS + 8) * sizeof(float));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_post_rows(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
+                           int lda, int dtype, void* stream) {
+    if (part == nullptr || x0 == nullptr || z == nullptr || pos == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || (long)B * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecArgs a = dec_args();
+    a.part = const_cast<float*>(part); a.vg = const_cast<void*>(vg); a.fb = fb; a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda;
+    HY_DEC_DISPATCH(decode_post_rows_kernel, dim3(1), DEC_POST_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
 }  // extern "C"

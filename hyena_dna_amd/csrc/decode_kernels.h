@@ -38,7 +38,7 @@ struct DecArgs {
     float* part;        // [nchunks][B][D] fp32 partial sums
     const float* fb;    // (D,) fp32 filter bias or null
     void* z;            // (B, D) I/O type
-    int* pos;           // the position t (device memory)
+    int* pos;           // the position t (device memory); the *_rows kernels: B positions, one per row
     int B, D, Bcap, Lcap, ldx, lda, ldk;
 };
 
@@ -157,6 +157,134 @@ __global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_kernel(DecArgs a
     }
     __syncthreads();
     if (threadIdx.x == 0 && valid) a.pos[0] = t + 1;
+}
+
+// ---- per-row positions: the same three kernels with t_b = pos[b] from a device int pos[B] (C ABI: hyena_decode_*_rows) --------------------
+// Row b of a batch of prompts of different lengths stands at its own position.  A row whose t_b is outside [0, Lcap) is parked: nothing of
+// it is read or written and its position stays.  With all t_b equal every kernel computes what its single-position twin above computes,
+// bit for bit (same arithmetic, same lanes, same summation order).
+
+// one thread per (b, d): grid ceil(B D / DEC_THREADS)
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_pre_rows_kernel(DecArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int i = (int)(blockIdx.x * DEC_THREADS + threadIdx.x);
+    if (i >= a.B * a.D) return;
+    const int b = i / a.D, d = i % a.D;
+    const int t = a.pos[b];
+    if (t < 0 || t >= a.Lcap) return;                                    // a parked row: its tail is not shifted
+    const elem_t* x = reinterpret_cast<const elem_t*>(a.x);
+    float o[3];
+    HY_UNROLL
+    for (int g = 0; g < 3; ++g) {
+        const int c = g * a.D + d;
+        float* tl = a.tail + ((size_t)c * a.Bcap + b) * 2;
+        const float xm2 = tl[0], xm1 = tl[1];
+        const float xn = Elem<DT>::dec(x[(size_t)b * a.ldx + c]);
+        o[g] = dec_sc(xm2, xm1, xn, t, a.w[c * 3], a.w[c * 3 + 1], a.w[c * 3 + 2], a.b[c], a.bin != nullptr ? a.bin[c] : 0.f);
+        tl[0] = xm1;
+        tl[1] = xn;
+    }
+    elem_t* vg = reinterpret_cast<elem_t*>(a.vg);
+    float p = o[1] * o[2];                                               // one fp32 product, then one conversion (decode_pre_kernel)
+#if !defined(HIPEMU)
+    asm volatile("" : "+v"(p));
+#endif
+    vg[((size_t)b * a.D + d) * a.lda + t] = Elem<DT>::cvt(p);
+    a.x0[(size_t)b * a.D + d] = o[0];
+}
+
+// grid (nchunks, D) as decode_conv_kernel.  The staged filter window k[c, t_b - s0 - CHUNK + 1 .. t_b - s0] depends on the row: it is staged
+// again only when t_b differs from the position whose window is in LDS.  Every branch around a barrier is taken on pos[b] as all threads
+// read it from the same address (nobody writes pos during this kernel), so it is uniform across the workgroup.
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_conv_rows_kernel(DecArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS;                                   // [2][4]: wavefront sums, alternating by the parity of the live row
+    const int chunk = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int s0 = chunk * DEC_CHUNK;
+    int tmax = -1;
+    for (int b = 0; b < a.B; ++b) {
+        const int t = a.pos[b];
+        if (t >= 0 && t < a.Lcap && t > tmax) tmax = t;
+    }
+    if (s0 > tmax) return;                                               // the chunk starts past every row: nothing staged, nothing loaded
+    const float* krow = a.k + (size_t)c * a.ldk;
+    int staged = -1, base = 0, live = 0;                                 // staged: the position whose window ks holds
+    for (int b = 0; b < a.B; ++b) {
+        const int t = a.pos[b];
+        if (t < 0 || t >= a.Lcap || s0 > t) continue;                    // parked, or the chunk starts past this row: no partial is written
+        if (t != staged) {
+            // (every wavefront's reads of the previous window lie before the barrier that closed the previous live row)
+            const int jlo = t - s0 - DEC_CHUNK + 1;
+            base = jlo >= 0 ? (jlo & ~3) : -((3 - jlo) & ~3);
+            const int ngroups = (t - s0 - base) / 4 + 1;
+            for (int q = tid; q < ngroups; q += DEC_THREADS) {
+                const int j = base + 4 * q;
+                float r[4] = {0.f, 0.f, 0.f, 0.f};
+                if (j >= 0) __builtin_memcpy(r, krow + j, sizeof(r));
+                HY_UNROLL
+                for (int e = 0; e < 4; ++e) ks[4 * q + e] = r[e];
+            }
+            __syncthreads();
+            staged = t;
+        }
+        const char* row = cm_row(a.vg, (size_t)b * a.D + c, a.lda, ES);
+        float acc = 0.f;
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            if (s <= t) {                                                 // (s + DEC_V <= lda: rows are 8-aligned and t < Lcap <= lda)
+                // aligned 16-byte loads; positions past t inside the last vector meet a zero tap (the history holds finite values only)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)s * ES, 16), sizeof(raw));
+                float x[DEC_V];
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) x[e] = Elem<DT>::dec(raw[e]);
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) {
+                    const bool ok = s + e <= t;
+                    const float kv = ks[ok ? t - s - e - base : 0];
+                    const float kk = ok ? kv : 0.f;
+                    acc = __builtin_fmaf(kk, x[e], acc);
+                }
+            }
+        }
+        acc = cm_wave_sum(acc);
+        HY_LDS float* rb = red + 4 * (live & 1);
+        ++live;
+        if ((tid & 63) == 0) rb[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) a.part[((size_t)chunk * a.B + b) * a.D + c] = (rb[0] + rb[1]) + (rb[2] + rb[3]);
+    }
+}
+
+// ONE workgroup: every thread reads the positions it needs before the barrier; after it, lane b advances pos[b] (the only access to pos[b]
+// past the barrier).  Row b sums the t_b / DEC_CHUNK + 1 partials decode_conv_rows wrote for it in this step and no other slot.
+template <int DT>
+__global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_rows_kernel(DecArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const elem_t* vg = reinterpret_cast<const elem_t*>(a.vg);
+    elem_t* z = reinterpret_cast<elem_t*>(a.z);
+    for (int i = threadIdx.x; i < a.B * a.D; i += DEC_POST_THREADS) {
+        const int b = i / a.D, d = i % a.D;
+        const int t = a.pos[b];
+        if (t < 0 || t >= a.Lcap) continue;
+        const int nc = t / DEC_CHUNK + 1;
+        float y = 0.f;
+        for (int ch = 0; ch < nc; ++ch) y += a.part[((size_t)ch * a.B + b) * a.D + d];
+        const float u = Elem<DT>::dec(vg[((size_t)b * a.D + d) * a.lda + t]);
+        if (a.fb != nullptr) y = __builtin_fmaf(u, a.fb[d], y);
+        const float yr = Elem<DT>::dec(Elem<DT>::cvt(y));                 // the forward's convolution output is stored in the I/O type
+        z[i] = Elem<DT>::cvt(yr * a.x0[i]);                                // cm_post_fwd: y * c0, rounded once
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < a.B; b += DEC_POST_THREADS) {
+        const int t = a.pos[b];
+        if (t >= 0 && t < a.Lcap) a.pos[b] = t + 1;
+    }
 }
 
 }  // namespace hyena

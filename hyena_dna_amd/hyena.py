@@ -482,7 +482,7 @@ class HyenaOperator(nn.Module):
             y, xT, vg = self._forward_fused_cm(u, l, keep_vg=True)
             if xT.dtype != st.dtype:
                 raise ValueError(f"the prefill runs in {xT.dtype}, the decode cache was built for {st.dtype}")
-            st.store_prefill(xT, vg, l)
+            st.store_prefill(xT, vg, l, lengths=getattr(ip, "lengths_per_sample", None))
         else:
             if l != 1:
                 raise ValueError(f"a decode step takes one position per sequence (got {l}); prefill with seqlen_offset = 0")

@@ -4,7 +4,8 @@ Every operation of the HyenaDNA model is per-position or causal, and the implici
 one ``l_max``-long table), so position t of a layer's long convolution is ``sum_{s <= t} k[c, t - s] vg[b, c, s] + fb[c] vg[b, c, t]``: a
 dot product over the history of the convolution's input ``vg = v * x1``.  ``HyenaDecodeState`` holds what that takes -- the filter
 ``filter_dl(max_seqlen)``, the history, the last two in_proj outputs the 3-tap short convolution still needs, the position (in device
-memory: one captured graph serves every position) and the step's small buffers -- and ``HyenaOperator.forward(u, inference_params=ip)``
+memory: one captured graph serves every position; one int for the batch, or one per row after a right-padded prefill with
+``InferenceParams.lengths_per_sample``) and the step's small buffers -- and ``HyenaOperator.forward(u, inference_params=ip)``
 fills it with a prefill (``ip.seqlen_offset == 0``) and advances it by one position per call afterwards (csrc/decode_kernels.h).
 """
 import torch
@@ -16,7 +17,10 @@ __all__ = ["InferenceParams", "HyenaDecodeState", "check_decodable"]
 
 class InferenceParams:
     """flash_attn.utils.generation.InferenceParams: ``max_seqlen``, ``max_batch_size``, ``seqlen_offset`` (alias ``sequence_len_offset``, the
-    older name), ``batch_size_offset``, ``key_value_memory_dict`` (layer key -> that layer's cache), ``lengths_per_sample``."""
+    older name), ``batch_size_offset``, ``key_value_memory_dict`` (layer key -> that layer's cache), ``lengths_per_sample``.
+
+    ``lengths_per_sample``: None, or the device int32 (B,) tensor of the prompts' own lengths when the prefill batch is right-padded.  The
+    prefill hands it to every layer's cache (``HyenaDecodeState.store_prefill``), which from then on keeps one position per row."""
 
     def __init__(self, max_seqlen, max_batch_size, seqlen_offset=0, batch_size_offset=0, key_value_memory_dict=None, lengths_per_sample=None):
         self.max_seqlen = max_seqlen
@@ -104,24 +108,51 @@ class HyenaDecodeState:
         self.hist = torch.zeros(self.B, D, _lib.row_pitch(L), dtype=self.dtype, device=dev)
         self.tail = torch.zeros(3 * D, self.B, 2, dtype=torch.float32, device=dev)
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pos_rows = torch.full((self.B,), -1, dtype=torch.int32, device=dev)   # ragged mode (store_prefill(lengths=...)): one position per row
+        self.ragged = False
         self.x0 = torch.empty(self.B, D, dtype=torch.float32, device=dev)
         self.z = torch.empty(self.B, D, dtype=self.dtype, device=dev)
         self.part = _lib.decode_partials(self.B, D, L, dev)
 
-    def store_prefill(self, xT, vg, P):
-        """after the prefill forward over P positions: its convolution input vg (B, D, P) and the last two in_proj outputs of xT (3D, B, P)"""
+    def store_prefill(self, xT, vg, P, lengths=None):
+        """after the prefill forward over P positions: its convolution input vg (B, D, P) and the last two in_proj outputs of xT (3D, B, P).
+
+        ``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): the prompts are right-padded to P and row b really holds lengths[b] positions.
+        The model is causal, so everything below lengths[b] is what the unpadded prompt gives; the cache then keeps one position per row
+        (``pos_rows``) and ``step`` runs the per-row kernels.  Device work only: nothing here reads ``lengths`` on the host."""
         B = vg.shape[0]
         self.hist[:B, :, :P].copy_(vg)
-        n = min(P, 2)
-        self.tail[:, :B].zero_()
-        self.tail[:, :B, 2 - n:].copy_(xT[:, :, P - n:P])
-        self.pos.fill_(P)
+        if lengths is None:
+            self.ragged = False
+            n = min(P, 2)
+            self.tail[:, :B].zero_()
+            self.tail[:, :B, 2 - n:].copy_(xT[:, :, P - n:P])
+            self.pos.fill_(P)
+            return
+        if lengths.shape != (B,) or lengths.dtype != torch.int32 or lengths.device != self.hist.device:
+            raise ValueError(f"lengths must be a ({B},) int32 tensor on {self.hist.device} (got {tuple(lengths.shape)} {lengths.dtype} on {lengths.device})")
+        self.ragged = True
+        # the pad positions' activations go: decode_conv reads up to 7 columns past t_b (times a zero tap) and relies on finite values there
+        cols = torch.arange(P, device=lengths.device, dtype=torch.int32)
+        self.hist[:B, :, :P].masked_fill_((cols[None, :] >= lengths[:, None])[:, None, :], 0)
+        # the tail of row b: columns lengths[b] - 2, lengths[b] - 1 of xT, zeros where they lie before position 0
+        idx = lengths.to(torch.int64)[:, None] + torch.tensor([-2, -1], device=lengths.device)            # (B, 2)
+        got = xT[:, :, :P].gather(2, idx.clamp(0, P - 1)[None].expand(xT.shape[0], B, 2)).to(torch.float32)
+        self.tail[:, :B].copy_(got * (idx >= 0)[None])
+        self.pos_rows.fill_(-1)                                                                            # rows past B stay parked
+        self.pos_rows[:B].copy_(lengths)
 
     def step(self, x2):
-        """x2 (B, 3D): in_proj output of the new position without bias -> z (B, D) for out_proj (three kernels; advances the position)"""
+        """x2 (B, 3D): in_proj output of the new position without bias -> z (B, D) for out_proj (three kernels; advances the position --
+        after a prefill with ``lengths``, every row's own)"""
         B = x2.shape[0]
+        z = self.z[:B]
+        if self.ragged:
+            _lib.decode_pre_rows(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos_rows, self.L)
+            _lib.decode_conv_rows(self.k, self.hist, self.part, self.pos_rows, B, self.L)
+            _lib.decode_post_rows(self.part, self.hist, self.fb, self.x0, z, self.pos_rows, B, self.L)
+            return z
         _lib.decode_pre(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L)
         _lib.decode_conv(self.k, self.hist, self.part, self.pos, B, self.L)
-        z = self.z[:B]
         _lib.decode_post(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.L)
         return z

@@ -367,9 +367,16 @@ class GenerationMixin:
 
     @torch.no_grad()
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
-                 cg=False, **kwargs):
+                 cg=False, lengths=None, pad_token_id=None, **kwargs):
+        """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
+        lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
+        (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
+        attribute where it has one, else 0).  Needs ``use_cache=True`` (each layer's cache keeps one position per row)."""
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
+        if lengths is not None:
+            return self._generate_ragged(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate,
+                                         output_scores, use_cache, cg)
         ids, scores = input_ids, []
         if not use_cache:
             while ids.shape[1] < max_length:
@@ -401,6 +408,62 @@ class GenerationMixin:
         if return_dict_in_generate:
             return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(ids, tuple(scores) if output_scores else None)
         return ids
+
+
+    def _generate_ragged(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
+                         use_cache, cg):
+        """generate() over right-padded prompts of different lengths: one prefill over the padded batch (causal model: the positions below
+        lengths[b] are those of the unpadded prompt), the first token of row b from the logits at position lengths[b] - 1, then per-row
+        decode steps.  One host check of ``lengths`` on entry; nothing in the loop reads them on the host."""
+        from .inference import InferenceParams
+        if not use_cache:
+            raise ValueError("generate(lengths=...) decodes every row at its own position, which only the cached step does: it needs use_cache=True")
+        B, P = input_ids.shape
+        if not torch.is_tensor(lengths) or lengths.shape != (B,) or lengths.dtype != torch.int32 or lengths.device != input_ids.device:
+            what = f"{tuple(lengths.shape)} {lengths.dtype} on {lengths.device}" if torch.is_tensor(lengths) else type(lengths).__name__
+            raise ValueError(f"lengths must be a ({B},) int32 tensor on {input_ids.device} (got {what})")
+        lo, hi = (int(v) for v in torch.stack([lengths.min(), lengths.max()]).tolist())            # the one host read
+        if lo < 1 or hi > P:
+            raise ValueError(f"lengths must lie in [1, {P}] (the padded prompt has {P} columns; got {lo} ... {hi})")
+        emb = getattr(getattr(self, "backbone", None), "embeddings", None)
+        if getattr(emb, "max_position_embeddings", 0) > 0:
+            raise NotImplementedError("generate(lengths=...) with learned position embeddings (one position id per row) is not implemented")
+        if pad_token_id is None:
+            pad_token_id = getattr(self, "pad_token_id", None)
+        pad_token_id = 0 if pad_token_id is None else int(pad_token_id)
+        N = max(int(max_length) - P, 0)
+        len64 = lengths.to(torch.int64)
+        cols = torch.arange(P + N, device=input_ids.device)
+        seq = torch.full((B, P + N), pad_token_id, dtype=input_ids.dtype, device=input_ids.device)
+        seq[:, :P] = torch.where(cols[None, :P] < len64[:, None], input_ids, seq[:, :P])
+        scores = []
+        if N > 0:
+            ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N)
+            if ip.key_value_memory_dict is None:
+                raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
+            out = self(input_ids, inference_params=ip)
+            logits = out[0] if isinstance(out, tuple) else out
+            logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V): row b's last prompt position
+            last = logits.gather(1, (len64 - 1)[:, None, None].expand(B, 1, logits.shape[-1]))[:, 0]
+            ip.seqlen_offset = P                       # the furthest any row has got: bounds checks only, the kernels read the per-row positions
+            step = GraphedDecodeStep(self, ip, B) if cg else None
+            try:
+                for i in range(N):
+                    logits, nxt = _sample(last, top_k, temperature)
+                    scores.append(logits)
+                    seq.scatter_(1, (len64 + i)[:, None], nxt)
+                    if i == N - 1:
+                        break
+                    last = step(nxt) if cg else _last_logits(self(nxt, inference_params=ip))
+                    ip.seqlen_offset += 1
+            finally:
+                if step is not None:
+                    step.release()
+        if return_dict_in_generate:
+            return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores", "lengths"])(
+                seq, tuple(scores) if output_scores else None, lengths + N)
+        return seq
 
 
 def sync_shared_params(model, process_group):
@@ -762,7 +825,8 @@ class GraphedDecodeStep:
     """The whole per-token step of cached generation -- embedding of a static (B, 1) token buffer, every layer's decode step, ln_f, the
     head -- captured into ONE hipGraph after the prefill and replayed once per token (``generate(use_cache=True, cg=True)``).  At short
     contexts the eager step is a few dozen launches of almost no work each; a replay is one.  The decode kernels read the position from
-    device memory, so the one graph serves every position; sampling stays outside.
+    device memory (one for the batch, or one per row after a prefill with ``lengths_per_sample``), so the one graph serves every position;
+    sampling stays outside.
 
         step = GraphedDecodeStep(model, ip, batch_size)      # after the prefill: warms up on the capture stream, captures
         logits = step(next_tokens)                           # (B, V) static buffer, overwritten by the next replay
@@ -789,12 +853,13 @@ class GraphedDecodeStep:
         self._side = side
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            snap = [(s.tail.clone(), s.pos.clone()) for s in states]
+            snap = [(s.tail.clone(), s.pos.clone(), s.pos_rows.clone()) for s in states]
             for _ in range(max(1, int(warmup))):
                 self._run()
-            for s, (tail, pos) in zip(states, snap):
+            for s, (tail, pos, pos_rows) in zip(states, snap):
                 s.tail.copy_(tail)
                 s.pos.copy_(pos)
+                s.pos_rows.copy_(pos_rows)
             side.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=side):

@@ -15,7 +15,15 @@
  *   k    : (D, ldk) fp32 filter (column j = tap j: HyenaFilter.filter_dl(Lcap)), ldk >= Lcap, ldk % 4 == 0, 16-byte aligned
  *   part : hyena_decode_partial_floats(B, D, Lcap) fp32 of scratch, [chunk][B][D] partial sums (no atomics: results are deterministic)
  *   fb   : (D,) fp32 filter bias or NULL;  z : (B, D) `dtype`, the out_proj operand of position t
- * 1 <= B <= Bcap, 1 <= Lcap <= 2^20.  Bad arguments return HYENA_ERR_BAD_ARG before anything is launched.  Asynchronous on `stream`. */
+ * 1 <= B <= Bcap, 1 <= Lcap <= 2^20.  Bad arguments return HYENA_ERR_BAD_ARG before anything is launched.  Asynchronous on `stream`.
+ *
+ * Per-row positions (hyena_decode_*_rows): the same three calls for a batch whose sequences stand at different positions.  `pos` points
+ * at B ints in device memory, row b is advanced from t_b = pos[b]: hyena_decode_pre_rows writes column t_b of row b's history,
+ * hyena_decode_conv_rows sums over s <= t_b (one partial per (chunk, b, d) with chunk * 8192 <= t_b; the other slots of `part` are neither
+ * written nor read), hyena_decode_post_rows reads those partials and vg[b, d, t_b] and then advances pos[b] by one.  A row whose t_b is
+ * outside [0, Lcap) is parked: its z row, history, tail and position stay as they are, the other rows advance.  History columns past t_b
+ * of row b must hold finite values (they may be read and are multiplied by a zero tap).  All other arguments, their checks and the
+ * stream semantics are those above; with all pos[b] equal the results equal the single-position entry points' bit for bit. */
 #ifndef HYENA_DECODE_H
 #define HYENA_DECODE_H
 #include <stddef.h>
@@ -33,6 +41,14 @@ int hyena_decode_conv(const float* k, int ldk, const void* vg, float* part, cons
 /* z = round(round(sum_chunks part + fb vg_t) * x0); then *pos = t + 1 */
 int hyena_decode_post(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap, int lda,
                       int dtype, void* stream);
+
+/* the three calls above with one position per row: pos points at B ints (see the header comment) */
+int hyena_decode_pre_rows(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vg, float* x0,
+                          const int* pos, int B, int Bcap, int D, int Lcap, int lda, int dtype, void* stream);
+int hyena_decode_conv_rows(const float* k, int ldk, const void* vg, float* part, const int* pos, int B, int D, int Lcap, int lda, int dtype,
+                           void* stream);
+int hyena_decode_post_rows(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
+                           int lda, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
