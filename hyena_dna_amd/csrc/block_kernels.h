@@ -170,6 +170,8 @@ __global__ void __launch_bounds__(BLK_THREADS) add_norm_bwd_kernel(AddNormArgs a
         blk_load<GDT, E>(a.x, off, g);
         blk_load<DT_F32, E>(a.saved, off, r);
         const float mean = a.mean[row], rstd = a.rstd[row];
+        // EMB: the row's token class, wave-uniform; -1: no class -- the forward left NaN in `saved`, the row joins no sum
+        const int v = EMB ? HY_SGPR((unsigned long long)a.ids[row] < (unsigned long long)a.V ? (int)a.ids[row] : -1) : 0;
         float s1 = 0.f, s2 = 0.f, xh[E];
         HY_UNROLL
         for (int e = 0; e < E; ++e) {
@@ -177,8 +179,14 @@ __global__ void __launch_bounds__(BLK_THREADS) add_norm_bwd_kernel(AddNormArgs a
             const float dxh = g[e] * w[e];
             s1 += dxh;
             s2 += dxh * xh[e];
-            dw[e] += g[e] * xh[e];
-            db[e] += g[e];
+            if (EMB) {                                       // the same operations on a copy, kept only for a row with a class (a select, no branch)
+                const float dwn = dw[e] + g[e] * xh[e], dbn = db[e] + g[e];
+                dw[e] = v >= 0 ? dwn : dw[e];
+                db[e] = v >= 0 ? dbn : db[e];
+            } else {
+                dw[e] += g[e] * xh[e];
+                db[e] += g[e];
+            }
         }
         s1 = wave_sum(s1) * inv_d;
         s2 = wave_sum(s2) * inv_d;
@@ -194,8 +202,6 @@ __global__ void __launch_bounds__(BLK_THREADS) add_norm_bwd_kernel(AddNormArgs a
         if (a.res_out != nullptr) blk_store<DT_F32, E>(a.res_out, off, dr);
         if (a.seed != nullptr) blk_dropout<E>(dr, off, seed, a.drop_below, a.keep_scale);      // d x0 = d residual' through the same mask
         if (EMB) {
-            const long long id = a.ids[row];
-            const int v = HY_SGPR((unsigned long long)id < (unsigned long long)a.V ? (int)id : -1);   // the row's token class: wave-uniform; -1: no class
             HY_UNROLL
             for (int q = 0; q < BLK_VMAX; ++q) {
                 if (v == q) {
