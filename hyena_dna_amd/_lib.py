@@ -180,6 +180,10 @@ def lib():
         for rows, one in ((L.hyena_decode_pre_rows, L.hyena_decode_pre), (L.hyena_decode_conv_rows, L.hyena_decode_conv),
                           (L.hyena_decode_post_rows, L.hyena_decode_post)):          # per-row positions: same arguments, pos -> B ints
             rows.restype, rows.argtypes = c_int, one.argtypes
+        L.hyena_decode_sample.restype = c_int
+        L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
+                                          c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
+                                          c_void_p, c_void_p, c_void_p]
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -858,6 +862,36 @@ def decode_post_rows(part, hist, fb, x0, z, pos, B, Lcap):
         check(lib().hyena_decode_post_rows(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
                                            z.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap), lda, dtype_code(hist.dtype),
                                            _backend.stream(z.device)))
+
+
+# ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------
+SAMPLE_MAX_V = 64
+
+
+def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, top_p=1.0, eos=-1, pad=0, vocab=None, scores=None, u_out=None):
+    """logits (B, V <= 64) fp32 / bf16 / fp16, rows contiguous -> row b's token at seq[b, col[b]] and nxt[b]; col advanced, done set on `eos`
+    (< 0: none); a parked row (col outside seq's columns) is left alone, a done row only gets nxt[b] = pad.  ``seed``: device int64 (1,);
+    ``col`` / ``done``: device int32 (B,); ``seq`` (B, ncols) and ``nxt`` (B,) or (B, 1): int64; ``vocab``: the live columns (default V);
+    ``scores`` (B, ncols, V) fp32 or None receives logits / T at [b, col[b]]; ``u_out`` (B,) fp32 or None the uniform each row drew."""
+    _require_gpu(logits, "logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    assert seed.dtype == torch.int64 and seed.numel() == 1
+    for t in (col, done):
+        assert t.dtype == torch.int32 and t.shape == (B,) and t.is_contiguous()
+    assert seq.dtype == torch.int64 and seq.dim() == 2 and seq.shape[0] == B and seq.stride(1) == 1
+    ncols = seq.shape[1]
+    assert nxt.dtype == torch.int64 and nxt.numel() == B and nxt.shape[0] == B
+    assert scores is None or (scores.dtype == torch.float32 and scores.shape == (B, ncols, V) and scores.is_contiguous())
+    assert u_out is None or (u_out.dtype == torch.float32 and u_out.shape == (B,) and u_out.is_contiguous())
+    for t in (seed, col, done, seq, nxt, scores, u_out):
+        assert t is None or t.device == logits.device
+    with _backend.guard(logits.device):
+        check(lib().hyena_decode_sample(logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, V,
+                                        V if vocab is None else int(vocab), float(temperature), int(top_k), float(top_p), seed.data_ptr(),
+                                        int(eos), int(pad), col.data_ptr(), done.data_ptr(), seq.data_ptr(), seq.stride(0) if B > 1 else ncols,
+                                        ncols, nxt.data_ptr(), nxt.stride(0) if B > 1 else 1, None if scores is None else scores.data_ptr(),
+                                        None if u_out is None else u_out.data_ptr(), _backend.stream(logits.device)))
 
 
 # ---- input projection on the matrix cores with the front of the shell in its epilogue (include/hyena_proj.h) --------------------

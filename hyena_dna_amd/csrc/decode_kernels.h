@@ -19,6 +19,7 @@
 // rows: k's global bytes do not scale with B and no global load is under-aligned.  (Storing k reversed at cache-build time would put both
 // streams in one direction but leave the t mod 4 offset, i.e. under-aligned 16-byte k loads, and k re-read per row or B accumulators per lane.)
 #pragma once
+#include "block_kernels.h"   // philox4x32_10
 #include "cm_kernels.h"
 
 namespace hyena {
@@ -284,6 +285,109 @@ __global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_rows_kernel(DecA
     for (int b = threadIdx.x; b < a.B; b += DEC_POST_THREADS) {
         const int t = a.pos[b];
         if (t >= 0 && t < a.Lcap) a.pos[b] = t + 1;
+    }
+}
+
+// ---- token sampling: the last node of the per-token graph (C ABI: hyena_decode_sample) ---------------------------------------------------
+// One wavefront per logit row (V <= 64: lane i holds logit i); workgroup = one wavefront, rows beyond the grid by a grid-stride loop.  The
+// row's column c = col[b] and its done flag live in device memory, like the decode positions: one captured graph serves every token, and
+// the token goes straight into the graph's static id buffer (`next`) and into column c of the preallocated sequence tensor.
+//   rank     r_i = #{ j < Vlive : l_j > l_i, or l_j == l_i and j < i }       (a permutation of 0 .. Vlive - 1; -inf logits rank by index)
+//   greedy   top_k <= 1: the token of rank 0; nothing random is drawn
+//   top-k    keep r_i < min(top_k, Vlive); p_i = exp((l_i - max l) / T) in fp32, summed IN RANK ORDER (every lane runs the same serial scan
+//            over LDS: the sums do not depend on lane count or reduction shape)
+//   top-p    the kept tokens whose preceding kept mass is < top_p Z: a prefix in rank order (the masses are >= 0), never empty
+//   draw     u = (word 0 of Philox4x32-10(counter (c, b), key seed) >> 8) 2^-24: a pure function of (seed, row, column); the first kept
+//            token whose inclusive cumulative mass exceeds u Z', else the last kept one
+// A parked row (c outside [0, ncols)) is neither read nor written; a done row writes next = pad and nothing else.  No atomics: lane 0 is the
+// only writer of the row's state, after every lane has read it.
+enum { SMP_VMAX = 64, SMP_MAX_GRID = 1 << 16, SMP_LDS_BYTES = 4 * SMP_VMAX * 4 };
+
+struct SampleArgs {
+    const void* logits;               // (B, V) I/O type, row b at b ldl
+    float* scores;                    // (B, ncols, V) fp32 or null: scores[b, c] = l / T
+    float* u_out;                     // (B,) fp32 or null: the uniform the row drew
+    const unsigned long long* seed;   // device pointer to the 64-bit seed
+    int* col;                         // (B,) the column row b writes next
+    int* done;                        // (B,) set once row b has emitted eos
+    long long* seq;                   // (B, ncols) token ids, row b at b lds
+    long long* next;                  // (B,) the model's next input ids, element b at b ldn
+    long ldl, lds, ldn;
+    int B, V, Vlive, ncols, top_k, eos, pad;
+    float T, top_p;
+};
+
+template <int DT>
+__global__ void __launch_bounds__(SMP_VMAX) decode_sample_kernel(SampleArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    HY_SMEM(smem);
+    HY_LDS float* sl = HY_LDS_CAST(float, smem);                 // [64] live logits by index
+    HY_LDS float* ss = sl + SMP_VMAX;                            // [64] logits by rank
+    HY_LDS float* sp = ss + SMP_VMAX;                            // [64] masses by rank
+    HY_LDS int* si = HY_LDS_CAST(int, smem) + 3 * SMP_VMAX;      // [64] token by rank
+    const int i = threadIdx.x;
+    const float ninf = -__builtin_inff();
+    // (every branch around a barrier is taken on col[b] / done[b] / top_k: uniform across the wavefront)
+    for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const int c = a.col[b];
+        if (c < 0 || c >= a.ncols) continue;                     // parked
+        if (a.done[b] != 0) {
+            if (i == 0) a.next[(size_t)b * a.ldn] = a.pad;
+            continue;
+        }
+        float l = ninf;
+        if (i < a.V) {
+            l = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.logits)[(size_t)b * a.ldl + i]);
+            if (a.scores != nullptr) a.scores[((size_t)b * a.ncols + c) * a.V + i] = l / a.T;
+        }
+        const bool live = i < a.Vlive;
+        sl[i] = live ? l : ninf;
+        __syncthreads();                                         // (also orders the previous row's scan before this row's ss / sp / si)
+        int r = 0;
+        for (int j = 0; j < a.Vlive; ++j) {
+            const float lj = sl[j];
+            r += (lj > l || (lj == l && j < i)) ? 1 : 0;
+        }
+        if (live) {
+            ss[r] = l;
+            si[r] = i;
+        }
+        __syncthreads();
+        int tok;
+        if (a.top_k <= 1) {
+            tok = si[0];
+        } else {
+            const int k = a.top_k < a.Vlive ? a.top_k : a.Vlive;
+            if (live) sp[r] = r < k ? expf((l - ss[0]) / a.T) : 0.f;
+            __syncthreads();
+            float Z = 0.f;
+            for (int q = 0; q < k; ++q) Z += sp[q];
+            const float lim = a.top_p * Z;
+            int nk = 0;
+            float kept = 0.f;                                    // Z': the mass of the nucleus
+            while (nk < k && kept < lim) kept += sp[nk++];
+            const unsigned long long seed = a.seed[0];
+            unsigned rnd[4];
+            philox4x32_10((unsigned)c, (unsigned)b, (unsigned)seed, (unsigned)(seed >> 32), rnd);
+            const float u = (float)(rnd[0] >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
+            const float target = u * kept;
+            tok = si[nk - 1];
+            float acc = 0.f;
+            for (int q = 0; q < nk; ++q) {
+                acc += sp[q];
+                if (acc > target) {
+                    tok = si[q];
+                    break;
+                }
+            }
+            if (i == 0 && a.u_out != nullptr) a.u_out[b] = u;
+        }
+        if (i == 0) {
+            a.seq[(size_t)b * a.lds + c] = tok;
+            a.next[(size_t)b * a.ldn] = tok;
+            a.col[b] = c + 1;
+            if (tok == a.eos) a.done[b] = 1;
+        }
     }
 }
 

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["InferenceParams", "HyenaDecodeState", "check_decodable"]
+__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable"]
 
 
 class InferenceParams:
@@ -156,3 +156,44 @@ class HyenaDecodeState:
         _lib.decode_conv(self.k, self.hist, self.part, self.pos, B, self.L)
         _lib.decode_post(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.L)
         return z
+
+
+class DeviceSampler:
+    """The token sampler of cached generation as one kernel per step (csrc/decode_kernels.h decode_sample_kernel; semantics in
+    include/hyena_decode.h): greedy / top-k / top-p with a seeded draw, EOS and padding, all of its state in device memory.
+
+    ``seq`` (B, ncols) int64 holds the prompts and ``pad`` elsewhere; ``col`` (int32 (B,)) the column every row writes next; ``done`` which
+    rows have emitted ``eos``; ``seed`` one int64.  ``sampler(logits, nxt)`` draws every row's token from ``logits`` (B, V <= 64), writes it to
+    ``seq[b, col[b]]`` and to ``nxt`` (the model's next input ids, (B, 1) int64) and advances ``col`` -- nothing is read on the host, so a
+    captured graph may end with the call (``GraphedDecodeStep(..., sampler=...)``)."""
+
+    def __init__(self, seq, col, seed, temperature=1.0, top_k=1, top_p=1.0, eos=None, pad=0, vocab=None, want_scores=False, V=None):
+        dev = seq.device
+        self.seq, self.col = seq, col
+        self.done = torch.zeros_like(col)
+        self.seed = seed
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        self.eos, self.pad, self.vocab = (-1 if eos is None else int(eos)), int(pad), vocab
+        self.scores = torch.zeros(seq.shape[0], seq.shape[1], V, dtype=torch.float32, device=dev) if want_scores else None
+
+    def __call__(self, logits, nxt):
+        _lib.decode_sample(logits, self.seed, self.col, self.done, self.seq, nxt, temperature=self.temperature, top_k=self.top_k,
+                           top_p=self.top_p, eos=self.eos, pad=self.pad, vocab=self.vocab, scores=self.scores)
+
+    def snapshot(self, steps):
+        """what up to ``steps`` calls from here may change -- col, done, the columns col[b] ... col[b] + steps - 1 of seq (and of scores) --
+        as a function that puts it back (``GraphedDecodeStep``'s warm-up steps run the real kernel)"""
+        ncols = self.seq.shape[1]
+        col, done = self.col.clone(), self.done.clone()
+        idx = (col.to(torch.int64)[:, None] + torch.arange(int(steps), device=col.device)).clamp_(0, ncols - 1)      # (B, steps)
+        seq = self.seq.gather(1, idx)
+        sidx = None if self.scores is None else idx[:, :, None].expand(-1, -1, self.scores.shape[2])
+        scores = None if self.scores is None else self.scores.gather(1, sidx)
+
+        def restore():
+            self.col.copy_(col)
+            self.done.copy_(done)
+            self.seq.scatter_(1, idx, seq)
+            if scores is not None:
+                self.scores.scatter_(1, sidx, scores)
+        return restore

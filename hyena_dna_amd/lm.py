@@ -367,13 +367,35 @@ class GenerationMixin:
 
     @torch.no_grad()
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
-                 cg=False, lengths=None, pad_token_id=None, **kwargs):
+                 cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
+                 stop_check_every=0, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
-        attribute where it has one, else 0).  Needs ``use_cache=True`` (each layer's cache keeps one position per row)."""
+        attribute where it has one, else 0).  Needs ``use_cache=True`` (each layer's cache keeps one position per row).
+
+        ``sampler``: ``"torch"`` -- torch ops between the steps (top-k, torch's global generator) -- or ``"device"``: one HIP kernel at the
+        end of every step (``inference.DeviceSampler``; with ``cg=True`` the last node of the replayed graph) that also serves ``top_p``
+        (nucleus sampling), ``eos_token_id`` (a row that emits it is finished: ``pad_token_id`` from there on, the other rows continue),
+        ``seed`` (the draws are a pure function of (seed, row, column); None: one seed from torch's generator per call) and ``vocab_size``
+        (logit columns from there on, the padded vocabulary, are never chosen).  None: ``"device"`` when any of those four is given, else
+        ``"torch"``.  ``stop_check_every=K > 0`` reads on the host every K tokens whether every row has finished and stops early (0: the
+        loop never reads anything back)."""
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
+        wants_device = [n for n, on in (("top_p", top_p is not None and float(top_p) != 1.0), ("eos_token_id", eos_token_id is not None),
+                                        ("seed", seed is not None), ("vocab_size", vocab_size is not None)) if on]
+        if sampler is None:
+            sampler = "device" if wants_device else "torch"
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"sampler={sampler!r}: 'torch', 'device' or None")
+        if sampler == "device":
+            return self._generate_device(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
+                                         use_cache, cg, 1.0 if top_p is None else float(top_p), eos_token_id, seed, vocab_size,
+                                         int(stop_check_every))
+        if wants_device or stop_check_every:
+            raise ValueError(f"sampler='torch' does not serve {', '.join(wants_device + ['stop_check_every'] * bool(stop_check_every))}: "
+                             "use sampler='device'")
         if lengths is not None:
             return self._generate_ragged(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate,
                                          output_scores, use_cache, cg)
@@ -408,6 +430,103 @@ class GenerationMixin:
         if return_dict_in_generate:
             return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(ids, tuple(scores) if output_scores else None)
         return ids
+
+
+    def _generate_device(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
+                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every):
+        """generate() with the device sampler: the prefill, one eager sampler call on its last logits (row b's own last position for ragged
+        prompts), then N - 1 steps that each end with the sampler kernel writing the next step's input ids in place -- with ``cg`` N - 1
+        graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front."""
+        from . import _lib
+        from .inference import DeviceSampler, InferenceParams
+        if not use_cache:
+            raise ValueError("generate(sampler='device') samples at the end of the cached step: it needs use_cache=True")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p={top_p}: the nucleus mass lies in (0, 1]")
+        if stop_check_every < 0:
+            raise ValueError(f"stop_check_every={stop_check_every}: a number of tokens, or 0 for never")
+        dev = input_ids.device
+        if not (dev.type == "cuda" or _lib._backend.name != "hip"):
+            raise NotImplementedError(f"generate(sampler='device') runs a HIP kernel: the model and input_ids must live on a ROCm device (got {dev})")
+        B, P = input_ids.shape
+        ragged = lengths is not None
+        if ragged:
+            if not torch.is_tensor(lengths) or lengths.shape != (B,) or lengths.dtype != torch.int32 or lengths.device != dev:
+                what = f"{tuple(lengths.shape)} {lengths.dtype} on {lengths.device}" if torch.is_tensor(lengths) else type(lengths).__name__
+                raise ValueError(f"lengths must be a ({B},) int32 tensor on {dev} (got {what})")
+            lo, hi = (int(v) for v in torch.stack([lengths.min(), lengths.max()]).tolist())        # the one host read
+            if lo < 1 or hi > P:
+                raise ValueError(f"lengths must lie in [1, {P}] (the padded prompt has {P} columns; got {lo} ... {hi})")
+            emb = getattr(getattr(self, "backbone", None), "embeddings", None)
+            if getattr(emb, "max_position_embeddings", 0) > 0:
+                raise NotImplementedError("generate(lengths=...) with learned position embeddings (one position id per row) is not implemented")
+        if pad_token_id is None:
+            pad_token_id = getattr(self, "pad_token_id", None)
+        pad_token_id = 0 if pad_token_id is None else int(pad_token_id)
+        N = max(int(max_length) - P, 0)
+        seq = torch.full((B, P + N), pad_token_id, dtype=torch.int64, device=dev)
+        if ragged:
+            cols = torch.arange(P, device=dev)
+            seq[:, :P] = torch.where(cols[None] < lengths[:, None], input_ids, seq[:, :P])
+            col = lengths.clone()
+        else:
+            seq[:, :P] = input_ids
+            col = torch.full((B,), P, dtype=torch.int32, device=dev)
+        smp, n_done = None, 0
+        if N > 0:
+            ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N)
+            if ip.key_value_memory_dict is None:
+                raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
+            out = self(input_ids, inference_params=ip)
+            logits = out[0] if isinstance(out, tuple) else out
+            logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V)
+            V = logits.shape[-1]
+            if V > _lib.SAMPLE_MAX_V:
+                raise ValueError(f"generate(sampler='device') serves logits of at most {_lib.SAMPLE_MAX_V} columns (this model has {V})")
+            if vocab_size is not None and not 1 <= int(vocab_size) <= V:
+                raise ValueError(f"vocab_size={vocab_size}: the logits have {V} columns")
+            if ragged:
+                last = logits.gather(1, (lengths.to(torch.int64) - 1)[:, None, None].expand(B, 1, V))[:, 0]
+            else:
+                last = logits[:, -1]
+            if seed is None:                           # torch's generator, once per call (greedy draws nothing)
+                seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if top_k > 1 else 0
+            seed = torch.tensor([int(seed)], dtype=torch.int64).to(dev)
+            smp = DeviceSampler(seq, col, seed, temperature=temperature, top_k=top_k, top_p=top_p, eos=eos_token_id, pad=pad_token_id,
+                                vocab=vocab_size, want_scores=output_scores, V=V)
+            ip.seqlen_offset = P                       # ragged: the furthest any row has got (bounds checks only)
+            step = GraphedDecodeStep(self, ip, B, sampler=smp) if cg and N > 1 else None
+            nxt = step.ids if step is not None else torch.empty(B, 1, dtype=torch.int64, device=dev)
+            try:
+                smp(last, nxt)
+                n_done = 1
+                for i in range(1, N):
+                    if stop_check_every and i % stop_check_every == 0 and bool(smp.done.all()):
+                        break
+                    if step is not None:
+                        step.replay()
+                    else:
+                        smp(_last_logits(self(nxt, inference_params=ip)), nxt)
+                    ip.seqlen_offset += 1
+                    n_done = i + 1
+            finally:
+                if step is not None:
+                    step.release()
+        if not return_dict_in_generate:
+            return seq
+        scores = None
+        if output_scores:
+            if smp is None:
+                scores = ()
+            elif ragged:                               # row b's i-th new token stands at column lengths[b] + i
+                idx = (lengths.to(torch.int64)[:, None] + torch.arange(n_done, device=dev))[:, :, None].expand(B, n_done, smp.scores.shape[2])
+                scores = tuple(smp.scores.gather(1, idx).unbind(1))
+            else:
+                scores = tuple(smp.scores[:, P:P + n_done].contiguous().unbind(1))
+        if ragged:
+            return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores", "lengths"])(seq, scores, lengths + N)
+        return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(seq, scores)
 
 
     def _generate_ragged(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
@@ -826,16 +945,18 @@ class GraphedDecodeStep:
     head -- captured into ONE hipGraph after the prefill and replayed once per token (``generate(use_cache=True, cg=True)``).  At short
     contexts the eager step is a few dozen launches of almost no work each; a replay is one.  The decode kernels read the position from
     device memory (one for the batch, or one per row after a prefill with ``lengths_per_sample``), so the one graph serves every position;
-    sampling stays outside.
+    sampling stays outside -- unless a ``sampler`` (``inference.DeviceSampler``) is given: then the graph ends with the sampling kernel, which
+    writes the next step's tokens into the static id buffer itself, and a token is ``step.replay()`` and nothing else.
 
         step = GraphedDecodeStep(model, ip, batch_size)      # after the prefill: warms up on the capture stream, captures
         logits = step(next_tokens)                           # (B, V) static buffer, overwritten by the next replay
         step.release()
 
-    Warm-up steps run the real kernels: the cache's tail state and position are put back afterwards (the history column they wrote is
-    rewritten by the first replay).  Same preconditions as ``GraphedTrainStep`` (``hyena_dna_amd.prepare_graph_runtime()``)."""
+    Warm-up steps run the real kernels: the cache's tail state and position (and the sampler's columns, done flags and the sequence columns
+    it wrote) are put back afterwards (the history column they wrote is rewritten by the first replay).  Same preconditions as
+    ``GraphedTrainStep`` (``hyena_dna_amd.prepare_graph_runtime()``)."""
 
-    def __init__(self, model, inference_params, batch_size, warmup=2):
+    def __init__(self, model, inference_params, batch_size, warmup=2, sampler=None):
         import hyena_dna_amd
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -844,7 +965,7 @@ class GraphedDecodeStep:
             raise RuntimeError("GraphedDecodeStep: hipGraph replays are only reliable on this ROCm runtime with DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 "
                                "in the environment before the HIP runtime initialises (hyena_dna_amd.prepare_graph_runtime(); INTEGRATION.md "
                                "section 6)")
-        self.model, self.ip = model, inference_params
+        self.model, self.ip, self.sampler = model, inference_params, sampler
         self.ids = torch.zeros(batch_size, 1, dtype=torch.long, device=dev)
         emb = model.backbone.embeddings
         self.pos_ids = torch.zeros(1, dtype=torch.long, device=dev) if emb.max_position_embeddings > 0 else None
@@ -854,12 +975,15 @@ class GraphedDecodeStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             snap = [(s.tail.clone(), s.pos.clone(), s.pos_rows.clone()) for s in states]
+            restore_sampler = sampler.snapshot(max(1, int(warmup))) if sampler is not None else None
             for _ in range(max(1, int(warmup))):
                 self._run()
             for s, (tail, pos, pos_rows) in zip(states, snap):
                 s.tail.copy_(tail)
                 s.pos.copy_(pos)
                 s.pos_rows.copy_(pos_rows)
+            if restore_sampler is not None:
+                restore_sampler()
             side.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=side):
@@ -868,7 +992,10 @@ class GraphedDecodeStep:
 
     def _run(self):
         out = self.model(self.ids, position_ids=self.pos_ids, inference_params=self.ip)
-        return out[0].logits[:, -1]
+        logits = out[0].logits[:, -1]
+        if self.sampler is not None:
+            self.sampler(logits, self.ids)
+        return logits
 
     def __call__(self, input_ids):
         """replays the step for the tokens input_ids (B, 1) at position ip.seqlen_offset; returns the static (B, V) logits"""
@@ -877,6 +1004,12 @@ class GraphedDecodeStep:
             self.pos_ids.fill_(int(self.ip.seqlen_offset))
         self.graph.replay()
         return self.logits
+
+    def replay(self):
+        """with a sampler: the step for the tokens the previous replay (or an eager sampler call on ``ids``) left in the id buffer"""
+        if self.pos_ids is not None:
+            self.pos_ids.fill_(int(self.ip.seqlen_offset))
+        self.graph.replay()
 
     def release(self):
         if self.graph is None:

@@ -50,6 +50,22 @@ int hyena_decode_conv_rows(const float* k, int ldk, const void* vg, float* part,
 int hyena_decode_post_rows(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
                            int lda, int dtype, void* stream);
 
+/* Token sampling, the last node of the per-token graph: one wavefront per row of `logits` (B, V) `dtype`, row b at b ldl, 1 <= Vlive <= V <= 64
+ * (columns >= Vlive, the padded vocabulary, are never chosen).  Row b stands at column c = col[b] of `seq` (B, ncols) int64, row b at b lds:
+ *   c outside [0, ncols): parked, nothing of the row is read or written;  done[b] != 0: next[b ldn] = pad and nothing else;  otherwise
+ *   scores[b, c, i] = l_i / T for i < V (scores (B, ncols, V) fp32 or NULL; T = max(temperature, 1e-6)), the token is drawn, and
+ *   seq[b, c] = next[b ldn] = tok, col[b] = c + 1, done[b] = 1 if tok == eos (eos < 0: none).
+ * The draw, with rank r_i = #{ j < Vlive : l_j > l_i, or l_j == l_i and j < i }: top_k <= 1 takes rank 0 (the maximum, lowest index on a tie;
+ * top_p and the seed do not matter).  Otherwise keep r_i < min(top_k, Vlive), p_i = exp((l_i - max l) / T) in fp32 over them and Z their sum;
+ * keep token i iff the kept mass ranked strictly before it is < top_p Z (0 < top_p <= 1); with u = (w >> 8) 2^-24, w word 0 of
+ * Philox4x32-10(counter (c, b, 0, 0), key *seed (low, high word)), the token is the kept one of smallest rank whose inclusive cumulative
+ * mass exceeds u Z' (Z' the kept mass), else the last kept one.  u_out (B,) fp32 or NULL receives u.  `seed` is a DEVICE pointer to one
+ * 64-bit word.  Logits are finite or -inf, at least one finite among the live ones.  Bad arguments (a null required pointer, V > 64, Vlive
+ * outside [1, V], top_p outside (0, 1], an unknown dtype, ldl < V, lds < ncols) return HYENA_ERR_BAD_ARG before anything is launched. */
+int hyena_decode_sample(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
+                        const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,
+                        long long* next, long ldn, float* scores, float* u_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
