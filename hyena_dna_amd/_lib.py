@@ -180,6 +180,16 @@ def lib():
         for rows, one in ((L.hyena_decode_pre_rows, L.hyena_decode_pre), (L.hyena_decode_conv_rows, L.hyena_decode_conv),
                           (L.hyena_decode_post_rows, L.hyena_decode_post)):          # per-row positions: same arguments, pos -> B ints
             rows.restype, rows.argtypes = c_int, one.argtypes
+        # fan-out: B = G fan rows, history columns [0, S) once per group, [S, Lcap) per row
+        L.hyena_decode_pre_fan.restype = c_int
+        L.hyena_decode_pre_fan.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+        L.hyena_decode_conv_fan.restype = c_int
+        L.hyena_decode_conv_fan.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_int, c_void_p]
+        L.hyena_decode_post_fan.restype = c_int
+        L.hyena_decode_post_fan.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_void_p]
         L.hyena_decode_sample.restype = c_int
         L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
@@ -782,6 +792,9 @@ def cm_pre_bwd(dvg, xT, bin_, w, b, dxT, part):
 
 
 # ---- one decode position (include/hyena_decode.h): hist is the (Bcap, D, lda) history of the convolution's input, pos a one-int device tensor ----
+DECODE_CHUNK = 8192          # history positions per decode_conv workgroup (DEC_CHUNK); the granularity of the fan-out's shared history
+
+
 def decode_partials(B, D, Lcap, device):
     return torch.empty(lib().hyena_decode_partial_floats(int(B), int(D), int(Lcap)), dtype=torch.float32, device=device)
 
@@ -862,6 +875,46 @@ def decode_post_rows(part, hist, fb, x0, z, pos, B, Lcap):
         check(lib().hyena_decode_post_rows(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
                                            z.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap), lda, dtype_code(hist.dtype),
                                            _backend.stream(z.device)))
+
+
+# ---- the same step for B = G fan rows (hyena_decode_*_fan): hist_s (G, D, lds) holds columns [0, S) of every group (None when S == 0),
+# hist_r (Bcap, D, ldr) columns [S, Lcap) of every row, column t at index t - S; pos a one-int device tensor ----
+def decode_pre_fan(x2, bin_, w, b, tail, hist_r, x0, pos, Lcap, S):
+    """decode_pre with the new column written to hist_r[:, :, t - S]"""
+    _require_gpu(x2, "x")
+    B, D3 = x2.shape
+    Bcap, D, ldr = _hist(hist_r)
+    assert D3 == 3 * D and x2.stride(1) == 1 and hist_r.dtype == x2.dtype
+    with _backend.guard(x2.device):
+        check(lib().hyena_decode_pre_fan(x2.data_ptr(), x2.stride(0), None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                         tail.data_ptr(), hist_r.data_ptr(), x0.data_ptr(), pos.data_ptr(), B, Bcap, D, int(Lcap), int(S), ldr,
+                                         dtype_code(x2.dtype), _backend.stream(x2.device)))
+
+
+def decode_conv_fan(k, hist_s, hist_r, part, pos, B, fan, Lcap, S):
+    """the partials of the chunks below S once per group, from hist_s, into part[chunk][g fan][d]; those from S on per row, from hist_r"""
+    _require_gpu(k, "k")
+    _, D, ldr = _hist(hist_r)
+    lds = 0
+    if hist_s is not None:
+        G, Ds, lds = _hist(hist_s)
+        assert Ds == D and hist_s.dtype == hist_r.dtype and G * int(fan) >= int(B)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv_fan(k.data_ptr(), k.stride(0), None if hist_s is None else hist_s.data_ptr(), hist_r.data_ptr(),
+                                          part.data_ptr(), pos.data_ptr(), int(B), int(fan), D, int(Lcap), int(S), lds, ldr,
+                                          dtype_code(hist_r.dtype), _backend.stream(k.device)))
+
+
+def decode_post_fan(part, hist_r, fb, x0, z, pos, B, fan, Lcap, S):
+    """decode_post with the partials of the chunks below S read from the group's slot and vg_t from hist_r[:, :, t - S]; advances pos"""
+    _require_gpu(z, "z")
+    _, D, ldr = _hist(hist_r)
+    assert z.dtype == hist_r.dtype and z.is_contiguous()
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post_fan(part.data_ptr(), hist_r.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(), z.data_ptr(),
+                                          pos.data_ptr(), int(B), int(fan), D, int(Lcap), int(S), ldr, dtype_code(hist_r.dtype),
+                                          _backend.stream(z.device)))
 
 
 # ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------

@@ -132,6 +132,19 @@ DecArgs dec_args() {
     a.B = a.D = a.Bcap = a.Lcap = a.ldx = a.lda = a.ldk = 0;
     return a;
 }
+// S: a whole number of chunks inside the cache; the row history holds columns [S, Lcap) in rows of ldr elements; the shared one [0, S)
+bool dec_fan_ok(bool shared, const void* vgs, const void* vgr, int B, int fan, int D, int Lcap, int S, int lds, int ldr, int dtype) {
+    if (vgr == nullptr || !dec_aligned16(vgr) || B < 1 || fan < 1 || B % fan != 0 || D < 1 || Lcap < 1 || Lcap > DEC_MAX_L || !dec_dtype_ok(dtype))
+        return false;
+    if (S < 0 || S % DEC_CHUNK != 0 || S > Lcap || ldr < 1 || ldr < Lcap - S || ldr % DEC_V != 0) return false;
+    return !shared || S == 0 || (vgs != nullptr && dec_aligned16(vgs) && lds >= S && lds % DEC_V == 0);   // (only decode_conv_fan reads it)
+}
+DecFanArgs dec_fan_args(const void* vgs, int fan, int S, int lds) {
+    DecFanArgs a;
+    static_cast<DecArgs&>(a) = dec_args();
+    a.vgs = vgs; a.fan = fan; a.S = S; a.lds = lds;
+    return a;
+}
 #define HY_DEC_DISPATCH(kernel, grid, threads, smem)                                                                  \
     do {                                                                                                              \
         switch (dtype) {                                                                                              \
@@ -217,6 +230,43 @@ int hyena_decode_post_rows(const float* part, const void* vg, const float* fb, c
     a.part = const_cast<float*>(part); a.vg = const_cast<void*>(vg); a.fb = fb; a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos;
     a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda;
     HY_DEC_DISPATCH(decode_post_rows_kernel, dim3(1), DEC_POST_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+// ---- fan-out: B = G fan rows, columns [0, S) of a group's history shared, [S, Lcap) per row (same grids) ---------------------------------
+int hyena_decode_pre_fan(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vgr, float* x0,
+                         const int* pos, int B, int Bcap, int D, int Lcap, int S, int ldr, int dtype, void* stream) {
+    if (x == nullptr || w == nullptr || b == nullptr || tail == nullptr || x0 == nullptr || pos == nullptr ||
+        !dec_fan_ok(false, nullptr, vgr, B, 1, D, Lcap, S, 0, ldr, dtype) || Bcap < B || ldx < 3 * D || (long)Bcap * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecFanArgs a = dec_fan_args(nullptr, 1, S, 0);
+    a.x = x; a.bin = bin; a.w = w; a.b = b; a.tail = tail; a.vg = vgr; a.x0 = x0; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Bcap = Bcap; a.Lcap = Lcap; a.ldx = ldx; a.lda = ldr;
+    HY_DEC_DISPATCH(decode_pre_fan_kernel, dim3((B * D + DEC_THREADS - 1) / DEC_THREADS), DEC_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_conv_fan(const float* k, int ldk, const void* vgs, const void* vgr, float* part, const int* pos, int B, int fan, int D,
+                          int Lcap, int S, int lds, int ldr, int dtype, void* stream) {
+    if (k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || pos == nullptr ||
+        !dec_fan_ok(true, vgs, vgr, B, fan, D, Lcap, S, lds, ldr, dtype) || D > 65535)
+        return HYENA_ERR_BAD_ARG;
+    DecFanArgs a = dec_fan_args(vgs, fan, S, lds);
+    a.k = k; a.vg = const_cast<void*>(vgr); a.part = part; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = ldr; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_conv_fan_kernel, dim3(dec_chunks(Lcap), D), DEC_THREADS, (DEC_KLDS + 8) * sizeof(float));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_post_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
+                          int Lcap, int S, int ldr, int dtype, void* stream) {
+    if (part == nullptr || x0 == nullptr || z == nullptr || pos == nullptr || !dec_fan_ok(false, nullptr, vgr, B, fan, D, Lcap, S, 0, ldr, dtype) ||
+        (long)B * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecFanArgs a = dec_fan_args(nullptr, fan, S, 0);
+    a.part = const_cast<float*>(part); a.vg = const_cast<void*>(vgr); a.fb = fb; a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = ldr;
+    HY_DEC_DISPATCH(decode_post_fan_kernel, dim3(1), DEC_POST_THREADS, 0);
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 

@@ -288,6 +288,138 @@ __global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_rows_kernel(DecA
     }
 }
 
+// ---- fan-out: n continuations of one prompt (C ABI: hyena_decode_*_fan) --------------------------------------------------------------------
+// G prompts, each fanned out to n = `fan` rows: B = G n, row b belongs to group b / n, one position t for the batch.  Below S (a multiple of
+// DEC_CHUNK, at most the prompt length) the n rows of a group hold the same history, so it is stored ONCE:
+//   shared   vgs (G, D, lds): columns [0, S) of group g            per row   vg (Bcap, D, lda): columns [S, Lcap) of row b, column s at s - S
+// A partial sum of decode_conv depends on one (chunk, row, channel) history segment and on t only, so the partial of a chunk below S is one
+// number for the n rows of a group: workgroup (chunk, c) with chunk < S / DEC_CHUNK computes it once per group, into slot [chunk][g n][c] of
+// the same `part` layout (the group's other slots of that chunk are neither written nor read), and decode_post_fan reads it from there for
+// every row of the group, in the same chunk order.  Same lanes, same FMA order, same wave sums as the single-position kernels: on a batch
+// whose rows hold the replicated history those give the same z, x0, tail, history column and position, bit for bit.
+// S is a multiple of DEC_CHUNK (so of 8): every 8-element vector of either tensor keeps its 16-byte alignment.  A position outside
+// [S, Lcap) makes the kernels do nothing (below S there is no row column to write).
+struct DecFanArgs : DecArgs {   // vg / lda: the per-row history and its pitch
+    const void* vgs;            // shared history (G, D, lds) I/O type, or null when S == 0
+    int fan, S, lds;
+};
+
+// one thread per (b, d): decode_pre_kernel's arithmetic, vg_t into column t - S of the row history
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_pre_fan_kernel(DecFanArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int i = (int)(blockIdx.x * DEC_THREADS + threadIdx.x);
+    const int t = a.pos[0];
+    if (i >= a.B * a.D || t < a.S || t >= a.Lcap) return;
+    const int b = i / a.D, d = i % a.D;
+    const elem_t* x = reinterpret_cast<const elem_t*>(a.x);
+    float o[3];
+    HY_UNROLL
+    for (int g = 0; g < 3; ++g) {
+        const int c = g * a.D + d;
+        float* tl = a.tail + ((size_t)c * a.Bcap + b) * 2;
+        const float xm2 = tl[0], xm1 = tl[1];
+        const float xn = Elem<DT>::dec(x[(size_t)b * a.ldx + c]);
+        o[g] = dec_sc(xm2, xm1, xn, t, a.w[c * 3], a.w[c * 3 + 1], a.w[c * 3 + 2], a.b[c], a.bin != nullptr ? a.bin[c] : 0.f);
+        tl[0] = xm1;
+        tl[1] = xn;
+    }
+    elem_t* vg = reinterpret_cast<elem_t*>(a.vg);
+    float p = o[1] * o[2];                                               // one fp32 product, then one conversion (decode_pre_kernel)
+#if !defined(HIPEMU)
+    asm volatile("" : "+v"(p));
+#endif
+    vg[((size_t)b * a.D + d) * a.lda + (t - a.S)] = Elem<DT>::cvt(p);
+    a.x0[(size_t)b * a.D + d] = o[0];
+}
+
+// grid (nchunks, D) as decode_conv_kernel; the filter window is staged once per workgroup (one t for the batch).  Workgroup (chunk, c) with
+// chunk < S / DEC_CHUNK loops over the G groups on the shared history, the others over the B rows on the row history.  The early exit and
+// the choice between the two are taken on pos[0], S and blockIdx: uniform across the workgroup; both loops have a uniform trip count and
+// one barrier per trip, as decode_conv_kernel's.
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_conv_fan_kernel(DecFanArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS;                                   // [2][4]: wavefront sums, alternating by the parity of the trip
+    const int t = a.pos[0];
+    const int chunk = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int s0 = chunk * DEC_CHUNK;
+    if (t < a.S || t >= a.Lcap || s0 > t) return;
+    const int jlo = t - s0 - DEC_CHUNK + 1;
+    const int base = jlo >= 0 ? (jlo & ~3) : -((3 - jlo) & ~3);
+    const int ngroups = (t - s0 - base) / 4 + 1;
+    const float* krow = a.k + (size_t)c * a.ldk;
+    for (int q = tid; q < ngroups; q += DEC_THREADS) {
+        const int j = base + 4 * q;
+        float r[4] = {0.f, 0.f, 0.f, 0.f};
+        if (j >= 0) __builtin_memcpy(r, krow + j, sizeof(r));
+        HY_UNROLL
+        for (int e = 0; e < 4; ++e) ks[4 * q + e] = r[e];
+    }
+    __syncthreads();
+    const bool shared = s0 < a.S;                                        // S is a multiple of DEC_CHUNK: the whole chunk lies on one side
+    const int nrows = shared ? a.B / a.fan : a.B;
+    const void* src = shared ? a.vgs : a.vg;
+    const int ld = shared ? a.lds : a.lda;
+    const int off = shared ? 0 : a.S;                                    // the tensor's column of history position s: s - off
+    for (int r = 0; r < nrows; ++r) {
+        const char* row = cm_row(src, (size_t)r * a.D + c, ld, ES);
+        float acc = 0.f;
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            if (s <= t) {                                                 // (s - off + DEC_V <= ld: 8-aligned rows; s <= t < S <= lds, or t - S < lda)
+                // aligned 16-byte loads; positions past t inside the last vector meet a zero tap (the history holds finite values only)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)(s - off) * ES, 16), sizeof(raw));
+                float x[DEC_V];
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) x[e] = Elem<DT>::dec(raw[e]);
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) {
+                    const bool ok = s + e <= t;
+                    const float kv = ks[ok ? t - s - e - base : 0];
+                    const float kk = ok ? kv : 0.f;
+                    acc = __builtin_fmaf(kk, x[e], acc);
+                }
+            }
+        }
+        acc = cm_wave_sum(acc);
+        HY_LDS float* rb = red + 4 * (r & 1);
+        if ((tid & 63) == 0) rb[tid >> 6] = acc;
+        __syncthreads();
+        const int slot = shared ? r * a.fan : r;
+        if (tid == 0) a.part[((size_t)chunk * a.B + slot) * a.D + c] = (rb[0] + rb[1]) + (rb[2] + rb[3]);
+    }
+}
+
+// ONE workgroup, as decode_post_kernel: the partial of chunk ch from the group's slot below S, from the row's own slot from S on
+template <int DT>
+__global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_fan_kernel(DecFanArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int t = a.pos[0];
+    const bool valid = t >= a.S && t < a.Lcap;
+    if (valid) {
+        const int nc = t / DEC_CHUNK + 1, ns = a.S / DEC_CHUNK;
+        const elem_t* vg = reinterpret_cast<const elem_t*>(a.vg);
+        elem_t* z = reinterpret_cast<elem_t*>(a.z);
+        for (int i = threadIdx.x; i < a.B * a.D; i += DEC_POST_THREADS) {
+            const int b = i / a.D, d = i % a.D;
+            const int bs = b / a.fan * a.fan;
+            float y = 0.f;
+            for (int ch = 0; ch < nc; ++ch) y += a.part[((size_t)ch * a.B + (ch < ns ? bs : b)) * a.D + d];
+            const float u = Elem<DT>::dec(vg[((size_t)b * a.D + d) * a.lda + (t - a.S)]);
+            if (a.fb != nullptr) y = __builtin_fmaf(u, a.fb[d], y);
+            const float yr = Elem<DT>::dec(Elem<DT>::cvt(y));                 // the forward's convolution output is stored in the I/O type
+            z[i] = Elem<DT>::cvt(yr * a.x0[i]);                                // cm_post_fwd: y * c0, rounded once
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && valid) a.pos[0] = t + 1;
+}
+
 // ---- token sampling: the last node of the per-token graph (C ABI: hyena_decode_sample) ---------------------------------------------------
 // One wavefront per logit row (V <= 64: lane i holds logit i); workgroup = one wavefront, rows beyond the grid by a grid-stride loop.  The
 // row's column c = col[b] and its done flag live in device memory, like the decode positions: one captured graph serves every token, and

@@ -452,12 +452,15 @@ class HyenaOperator(nn.Module):
         return y, xT, vg
 
     # ---- incremental decoding (hyena_dna_amd/inference.py, csrc/decode_kernels.h) ----------------------------------------------------------------
-    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, **kwargs):
         """A ``HyenaDecodeState`` for up to batch_size sequences of up to max_seqlen positions, to be put into
         ``InferenceParams.key_value_memory_dict`` under this operator's ``layer_idx`` (or the operator itself when it has none).  The cache is a
-        snapshot of the weights at this call, as a key-value cache is: build a new one after the weights change."""
+        snapshot of the weights at this call, as a key-value cache is: build a new one after the weights change.
+
+        ``fan = n > 1`` with ``prompt_len``: batch_size = G n rows that continue G prompts of prompt_len positions n times each; the prefill
+        then takes the G prompts, the steps all G n rows, and the history below (prompt_len // 8192) * 8192 is kept once per prompt."""
         from .inference import HyenaDecodeState
-        return HyenaDecodeState(self, batch_size, max_seqlen, dtype=dtype)
+        return HyenaDecodeState(self, batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len)
 
     def _decode_key(self):
         return self.layer_idx if getattr(self, "layer_idx", None) is not None else self
@@ -476,6 +479,9 @@ class HyenaOperator(nn.Module):
         if B > st.B:
             raise ValueError(f"a batch of {B} sequences does not fit a decode cache built for {st.B}")
         off = int(ip.seqlen_offset)
+        if st.fan > 1 and B != (st.B // st.fan if off == 0 else st.B):
+            raise ValueError(f"a decode cache with fan = {st.fan} for {st.B} rows takes a prefill of exactly {st.B // st.fan} prompts "
+                             f"(batch_size / fan) and steps of all {st.B} rows (got {B} at offset {off})")
         if off == 0:
             if not 1 <= l <= st.L:
                 raise ValueError(f"a prompt of {l} positions does not fit a decode cache of {st.L}")

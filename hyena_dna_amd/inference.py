@@ -81,12 +81,29 @@ class HyenaDecodeState:
     every step must run in it.
 
     Memory: k (D, max_seqlen) fp32 + history (batch_size, D, max_seqlen) in ``dtype`` + O(B D) -- at 2^20 x 256 with B = 1 in bf16, 1 GiB
-    plus 0.5 GiB per layer."""
+    plus 0.5 GiB per layer.
 
-    def __init__(self, op, batch_size, max_seqlen, dtype=None):
+    ``fan = n > 1``: the batch is G = batch_size / n prompts of ``prompt_len`` positions, each continued n times (row g n + j: sample j of
+    prompt g).  The prefill runs over the G prompts; the history below ``S = (prompt_len // 8192) * 8192`` is the same for the n rows of a
+    group and is kept once -- ``hist_shared`` (G, D, S) -- and ``hist`` (batch_size, D, max_seqlen - S) holds every row's columns from S
+    on.  The step runs the ``_fan`` kernels, whose results equal those of the plain step on the replicated history bit for bit.  A prompt
+    shorter than 8192 positions has S = 0: nothing is shared in the step (which is launch-bound there), the prefill is still paid once."""
+
+    def __init__(self, op, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None):
         check_decodable(op, max_seqlen)
         if int(batch_size) < 1:
             raise ValueError(f"batch_size={batch_size}: at least one sequence")
+        self.fan = int(fan)
+        if self.fan < 1:
+            raise ValueError(f"fan={fan}: at least one continuation per prompt")
+        self.S = 0
+        if self.fan > 1:
+            if int(batch_size) % self.fan != 0:
+                raise ValueError(f"batch_size={batch_size} is not a multiple of fan={fan} (batch_size counts the rows: prompts x fan)")
+            if prompt_len is None or not 1 <= int(prompt_len) <= int(max_seqlen):
+                raise ValueError(f"prompt_len={prompt_len}: a cache with fan > 1 is laid out for one prompt length in 1 ... max_seqlen = {max_seqlen}")
+            self.prompt_len = int(prompt_len)
+            self.S = self.prompt_len // _lib.DECODE_CHUNK * _lib.DECODE_CHUNK
         dev = op.in_proj.weight.device
         self.dtype = dtype if dtype is not None else _default_dtype(op, dev)
         if self.dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -105,7 +122,9 @@ class HyenaDecodeState:
             self.bin = op.in_proj.bias.detach().to(torch.float32).clone() if op.in_proj.bias is not None else None
             self.w = op.short_filter.weight.detach().to(torch.float32).reshape(3 * D, 3).clone()
             self.b = op.short_filter.bias.detach().to(torch.float32).clone()
-        self.hist = torch.zeros(self.B, D, _lib.row_pitch(L), dtype=self.dtype, device=dev)
+        # fan > 1: columns [0, S) once per group, [S, L) per row (at least one column, so that the row tensor always exists)
+        self.hist_shared = torch.zeros(self.B // self.fan, D, _lib.row_pitch(self.S), dtype=self.dtype, device=dev) if self.S > 0 else None
+        self.hist = torch.zeros(self.B, D, _lib.row_pitch(max(L - self.S, 1)), dtype=self.dtype, device=dev)
         self.tail = torch.zeros(3 * D, self.B, 2, dtype=torch.float32, device=dev)
         self.pos = torch.zeros(1, dtype=torch.int32, device=dev)
         self.pos_rows = torch.full((self.B,), -1, dtype=torch.int32, device=dev)   # ragged mode (store_prefill(lengths=...)): one position per row
@@ -121,6 +140,23 @@ class HyenaDecodeState:
         The model is causal, so everything below lengths[b] is what the unpadded prompt gives; the cache then keeps one position per row
         (``pos_rows``) and ``step`` runs the per-row kernels.  Device work only: nothing here reads ``lengths`` on the host."""
         B = vg.shape[0]
+        if self.fan > 1:
+            if lengths is not None:
+                raise NotImplementedError("a decode cache with fan > 1 holds prompts of one length: ragged prompts with fan-out are out of scope")
+            G, n, S = self.B // self.fan, self.fan, self.S
+            if B != G or P != self.prompt_len:
+                raise ValueError(f"this decode cache was built for a prefill of {G} prompts (batch_size / fan) of {self.prompt_len} positions "
+                                 f"(got {B} of {P})")
+            if S > 0:
+                self.hist_shared[:, :, :S].copy_(vg[:, :, :S])
+            if P > S:
+                self.hist.view(G, n, self.D, -1)[:, :, :, :P - S].copy_(vg[:, None, :, S:P])
+            m = min(P, 2)
+            self.tail.zero_()
+            self.tail.view(-1, G, n, 2)[:, :, :, 2 - m:].copy_(xT[:, :, None, P - m:P])
+            self.ragged = False
+            self.pos.fill_(P)
+            return
         self.hist[:B, :, :P].copy_(vg)
         if lengths is None:
             self.ragged = False
@@ -147,6 +183,13 @@ class HyenaDecodeState:
         after a prefill with ``lengths``, every row's own)"""
         B = x2.shape[0]
         z = self.z[:B]
+        if self.fan > 1:
+            if B != self.B:
+                raise ValueError(f"a step of a decode cache with fan = {self.fan} takes all {self.B} rows (got {B})")
+            _lib.decode_pre_fan(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L, self.S)
+            _lib.decode_conv_fan(self.k, self.hist_shared, self.hist, self.part, self.pos, B, self.fan, self.L, self.S)
+            _lib.decode_post_fan(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.fan, self.L, self.S)
+            return z
         if self.ragged:
             _lib.decode_pre_rows(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos_rows, self.L)
             _lib.decode_conv_rows(self.k, self.hist, self.part, self.pos_rows, B, self.L)

@@ -368,7 +368,7 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
                  cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
-                 stop_check_every=0, **kwargs):
+                 stop_check_every=0, num_return_sequences=1, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
@@ -380,9 +380,26 @@ class GenerationMixin:
         ``seed`` (the draws are a pure function of (seed, row, column); None: one seed from torch's generator per call) and ``vocab_size``
         (logit columns from there on, the padded vocabulary, are never chosen).  None: ``"device"`` when any of those four is given, else
         ``"torch"``.  ``stop_check_every=K > 0`` reads on the host every K tokens whether every row has finished and stops early (0: the
-        loop never reads anything back)."""
+        loop never reads anything back).
+
+        ``num_return_sequences=n > 1``: n continuations of every prompt.  ``input_ids`` (G, P) -> ``sequences`` (G n, max_length), row
+        g n + j being sample j of prompt g; ``scores`` are those of a batch of G n rows.  Needs ``use_cache=True``: the prefill runs once
+        over the G prompts, every row's first token is drawn from its prompt's last logits, and each layer's cache keeps the history below
+        ``(P // 8192) * 8192`` once per prompt (``HyenaDecodeState`` with ``fan=n``), so neither the prefill, nor the cache, nor the bytes
+        a step streams below that point grow with n.  The step's results are those of ``generate(input_ids.repeat_interleave(n, 0))`` bit
+        for bit.  Under the device sampler the rows of a group differ because the draw depends on the row index (under ``"torch"``
+        through the global generator); greedy rows are all equal.  A prompt shorter than 8192 positions shares nothing in the step, which
+        is launch-bound there -- it still saves the prefill.  Not together with ``lengths``."""
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
+        n = int(num_return_sequences)
+        if n < 1:
+            raise ValueError(f"num_return_sequences={num_return_sequences}: at least one continuation per prompt")
+        if n > 1 and not use_cache:
+            raise ValueError("generate(num_return_sequences > 1) shares the prompt through the decode cache: it needs use_cache=True")
+        if n > 1 and lengths is not None:
+            raise NotImplementedError("generate(num_return_sequences > 1, lengths=...): ragged prompts with fan-out are out of scope "
+                                      "(the shared history needs one prompt length)")
         wants_device = [n for n, on in (("top_p", top_p is not None and float(top_p) != 1.0), ("eos_token_id", eos_token_id is not None),
                                         ("seed", seed is not None), ("vocab_size", vocab_size is not None)) if on]
         if sampler is None:
@@ -392,7 +409,7 @@ class GenerationMixin:
         if sampler == "device":
             return self._generate_device(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
                                          use_cache, cg, 1.0 if top_p is None else float(top_p), eos_token_id, seed, vocab_size,
-                                         int(stop_check_every))
+                                         int(stop_check_every), fan=n)
         if wants_device or stop_check_every:
             raise ValueError(f"sampler='torch' does not serve {', '.join(wants_device + ['stop_check_every'] * bool(stop_check_every))}: "
                              "use sampler='device'")
@@ -407,12 +424,14 @@ class GenerationMixin:
                 ids = torch.cat([ids, nxt], dim=1)
         elif ids.shape[1] < max_length:
             from .inference import InferenceParams
-            B = ids.shape[0]
+            B = ids.shape[0] * n
             ip = InferenceParams(max_seqlen=max_length, max_batch_size=B)
-            ip.key_value_memory_dict = self.allocate_inference_cache(B, max_length)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, max_length, **({} if n == 1 else dict(fan=n, prompt_len=ids.shape[1])))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
             last = _last_logits(self(ids, inference_params=ip))
+            if n > 1:                                  # one prefill over the G prompts; from here on G n rows
+                last, ids = last.repeat_interleave(n, 0), ids.repeat_interleave(n, 0)
             ip.seqlen_offset = ids.shape[1]
             step = GraphedDecodeStep(self, ip, B) if cg else None
             try:
@@ -427,16 +446,19 @@ class GenerationMixin:
             finally:
                 if step is not None:
                     step.release()
+        elif n > 1:                                    # nothing to generate: the rows of a group are the prompt
+            ids = ids.repeat_interleave(n, 0)
         if return_dict_in_generate:
             return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(ids, tuple(scores) if output_scores else None)
         return ids
 
 
     def _generate_device(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
-                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every):
+                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1):
         """generate() with the device sampler: the prefill, one eager sampler call on its last logits (row b's own last position for ragged
         prompts), then N - 1 steps that each end with the sampler kernel writing the next step's input ids in place -- with ``cg`` N - 1
-        graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front."""
+        graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front.  ``fan = n > 1``:
+        ``input_ids`` holds G prompts, B = G n rows; the prefill runs over the prompts and row g n + j draws from prompt g's last logits."""
         from . import _lib
         from .inference import DeviceSampler, InferenceParams
         if not use_cache:
@@ -449,6 +471,7 @@ class GenerationMixin:
         if not (dev.type == "cuda" or _lib._backend.name != "hip"):
             raise NotImplementedError(f"generate(sampler='device') runs a HIP kernel: the model and input_ids must live on a ROCm device (got {dev})")
         B, P = input_ids.shape
+        B *= fan
         ragged = lengths is not None
         if ragged:
             if not torch.is_tensor(lengths) or lengths.shape != (B,) or lengths.dtype != torch.int32 or lengths.device != dev:
@@ -470,17 +493,17 @@ class GenerationMixin:
             seq[:, :P] = torch.where(cols[None] < lengths[:, None], input_ids, seq[:, :P])
             col = lengths.clone()
         else:
-            seq[:, :P] = input_ids
+            seq[:, :P] = input_ids if fan == 1 else input_ids.repeat_interleave(fan, 0)
             col = torch.full((B,), P, dtype=torch.int32, device=dev)
         smp, n_done = None, 0
         if N > 0:
             ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths)
-            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N, **({} if fan == 1 else dict(fan=fan, prompt_len=P)))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
             out = self(input_ids, inference_params=ip)
             logits = out[0] if isinstance(out, tuple) else out
-            logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V)
+            logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V); fan > 1: (B / fan, P, V)
             V = logits.shape[-1]
             if V > _lib.SAMPLE_MAX_V:
                 raise ValueError(f"generate(sampler='device') serves logits of at most {_lib.SAMPLE_MAX_V} columns (this model has {V})")
@@ -489,7 +512,7 @@ class GenerationMixin:
             if ragged:
                 last = logits.gather(1, (lengths.to(torch.int64) - 1)[:, None, None].expand(B, 1, V))[:, 0]
             else:
-                last = logits[:, -1]
+                last = logits[:, -1] if fan == 1 else logits[:, -1].repeat_interleave(fan, 0)
             if seed is None:                           # torch's generator, once per call (greedy draws nothing)
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if top_k > 1 else 0
             seed = torch.tensor([int(seed)], dtype=torch.int64).to(dev)
@@ -761,10 +784,12 @@ class HyenaDNALM(nn.Module, GenerationMixin):
     def _mixers(self):
         return [getattr(blk.mixer, "layer", blk.mixer) for blk in self.backbone.layers]      # (a CheckpointedModule is unwrapped)
 
-    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, **kwargs):
         """{layer key: HyenaDecodeState} for InferenceParams.key_value_memory_dict (flash_attn's generate assigns it that way).  Every layer must
-        be servable (HyenaOperator._forward_cached's refusals apply here, up front).  The caches are snapshots of the weights at this call."""
-        return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype) for m in self._mixers()}
+        be servable (HyenaOperator._forward_cached's refusals apply here, up front).  The caches are snapshots of the weights at this call.
+        ``fan`` / ``prompt_len``: batch_size = G fan rows continue G prompts of prompt_len positions (``HyenaOperator.allocate_inference_cache``)."""
+        return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len)
+                for m in self._mixers()}
 
     def forward(self, input_ids, position_ids=None, inference_params=None, state=None):
         # (the head through projection.hyena_linear: its weight gradient contracts 16 x 256 outputs over 10^6 tokens, which the GEMM library

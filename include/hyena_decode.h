@@ -23,7 +23,21 @@
  * written nor read), hyena_decode_post_rows reads those partials and vg[b, d, t_b] and then advances pos[b] by one.  A row whose t_b is
  * outside [0, Lcap) is parked: its z row, history, tail and position stay as they are, the other rows advance.  History columns past t_b
  * of row b must hold finite values (they may be read and are multiplied by a zero tap).  All other arguments, their checks and the
- * stream semantics are those above; with all pos[b] equal the results equal the single-position entry points' bit for bit. */
+ * stream semantics are those above; with all pos[b] equal the results equal the single-position entry points' bit for bit.
+ *
+ * Fan-out (hyena_decode_*_fan): the same three calls for G prompts that are each continued n = `fan` times.  B = G fan rows, row b belongs
+ * to group b / fan, and all rows stand at the one position *pos.  Below S -- a multiple of 8192 (the history chunk), 0 <= S <= Lcap, in
+ * practice (prompt length / 8192) 8192 -- the rows of a group have the same history, and it is kept once:
+ *   vgs  : shared history (G, D, lds) `dtype`, columns [0, S) of group g in row (g D + d) lds; lds >= S, lds % 8 == 0, 16-byte aligned;
+ *          read by hyena_decode_conv_fan only, may be NULL when S == 0
+ *   vgr  : per-row history (Bcap, D, ldr) `dtype`, column t >= S of row b at index t - S of row (b D + d) ldr; ldr >= max(Lcap - S, 1),
+ *          ldr % 8 == 0, 16-byte aligned; hyena_decode_pre_fan writes index t - S
+ * hyena_decode_conv_fan computes the partial of a chunk below S once per group, into slot [chunk][g fan][d] of `part` (the layout and size
+ * of hyena_decode_partial_floats(B, D, Lcap); the group's other slots of that chunk are neither written nor read), and one partial per
+ * row for the chunks from S on; hyena_decode_post_fan sums row b's partials in chunk order, taking chunk < S / 8192 from slot g fan.  On
+ * the batch whose B rows hold the replicated history the single-position entry points give the same z, x0, tail, history column and
+ * position, bit for bit.  A position outside [S, Lcap) makes the kernels do nothing.  Bad arguments -- those above, and S not a multiple of
+ * 8192, S > Lcap, fan < 1, B not a multiple of fan, a misaligned pointer or pitch -- return HYENA_ERR_BAD_ARG before anything is launched. */
 #ifndef HYENA_DECODE_H
 #define HYENA_DECODE_H
 #include <stddef.h>
@@ -49,6 +63,14 @@ int hyena_decode_conv_rows(const float* k, int ldk, const void* vg, float* part,
                            void* stream);
 int hyena_decode_post_rows(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
                            int lda, int dtype, void* stream);
+
+/* the three calls above for B = G fan rows: history columns [0, S) once per group (vgs), [S, Lcap) per row (vgr) (see the header comment) */
+int hyena_decode_pre_fan(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vgr, float* x0,
+                         const int* pos, int B, int Bcap, int D, int Lcap, int S, int ldr, int dtype, void* stream);
+int hyena_decode_conv_fan(const float* k, int ldk, const void* vgs, const void* vgr, float* part, const int* pos, int B, int fan, int D,
+                          int Lcap, int S, int lds, int ldr, int dtype, void* stream);
+int hyena_decode_post_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
+                          int Lcap, int S, int ldr, int dtype, void* stream);
 
 /* Token sampling, the last node of the per-token graph: one wavefront per row of `logits` (B, V) `dtype`, row b at b ldl, 1 <= Vlive <= V <= 64
  * (columns >= Vlive, the padded vocabulary, are never chosen).  Row b stands at column c = col[b] of `seq` (B, ncols) int64, row b at b lds:
