@@ -190,6 +190,13 @@ def lib():
         L.hyena_decode_post_fan.restype = c_int
         L.hyena_decode_post_fan.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_void_p]
+        # block step: T positions per call -- the arguments of the single-position / fan call with T before dtype
+        L.hyena_decode_block_partial_floats.restype = c_size_t
+        L.hyena_decode_block_partial_floats.argtypes = [c_int, c_int, c_int, c_int]
+        for blk, one in ((L.hyena_decode_pre_block, L.hyena_decode_pre), (L.hyena_decode_conv_block, L.hyena_decode_conv),
+                         (L.hyena_decode_post_block, L.hyena_decode_post), (L.hyena_decode_pre_block_fan, L.hyena_decode_pre_fan),
+                         (L.hyena_decode_conv_block_fan, L.hyena_decode_conv_fan), (L.hyena_decode_post_block_fan, L.hyena_decode_post_fan)):
+            blk.restype, blk.argtypes = c_int, one.argtypes[:-1] + [c_int, c_void_p]
         L.hyena_decode_sample.restype = c_int
         L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
@@ -915,6 +922,99 @@ def decode_post_fan(part, hist_r, fb, x0, z, pos, B, fan, Lcap, S):
         check(lib().hyena_decode_post_fan(part.data_ptr(), hist_r.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(), z.data_ptr(),
                                           pos.data_ptr(), int(B), int(fan), D, int(Lcap), int(S), ldr, dtype_code(hist_r.dtype),
                                           _backend.stream(z.device)))
+
+
+# ---- the block step (hyena_decode_*_block, *_block_fan): T positions per call.  x3 (B, T, 3D) the in_proj output without bias, x0 / z (B, T, D)
+# contiguous, part from decode_block_partials; bit for bit what T single-position calls leave ----
+DECODE_TMAX = 64             # HYENA_DECODE_TMAX: positions per block step
+
+
+def decode_block_partials(B, D, Lcap, T, device):
+    return torch.empty(lib().hyena_decode_block_partial_floats(int(B), int(D), int(Lcap), int(T)), dtype=torch.float32, device=device)
+
+
+def _block_x(x3, hist):
+    B, T, D3 = x3.shape
+    assert x3.is_contiguous() and hist.dtype == x3.dtype and D3 == 3 * hist.shape[1]
+    return B, T, D3
+
+
+def _block_out(x0, z, B, T, D, hist):
+    assert x0.dtype == torch.float32 and x0.shape == (B, T, D) and x0.is_contiguous()
+    assert z is None or (z.dtype == hist.dtype and z.shape == (B, T, D) and z.is_contiguous())
+
+
+def decode_pre_block(x3, bin_, w, b, tail, hist, x0, pos, Lcap):
+    """hist[:, :, t0 ... t0 + T - 1] = v * x1 of the block's positions, x0 (B, T, D) fp32, tail = positions t0 + T - 2, t0 + T - 1"""
+    _require_gpu(x3, "x")
+    Bcap, D, lda = _hist(hist)
+    B, T, ldx = _block_x(x3, hist)
+    _block_out(x0, None, B, T, D, hist)
+    with _backend.guard(x3.device):
+        check(lib().hyena_decode_pre_block(x3.data_ptr(), ldx, None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                           tail.data_ptr(), hist.data_ptr(), x0.data_ptr(), pos.data_ptr(), B, Bcap, D, int(Lcap), lda, T,
+                                           dtype_code(x3.dtype), _backend.stream(x3.device)))
+
+
+def decode_conv_block(k, hist, part, pos, B, T, Lcap):
+    """part[chunk][b][i][d] = the chunk's share of sum_{s <= t0 + i} k[d, t0 + i - s] hist[b, d, s]: the history is read once for the T outputs"""
+    _require_gpu(k, "k")
+    _, D, lda = _hist(hist)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv_block(k.data_ptr(), k.stride(0), hist.data_ptr(), part.data_ptr(), pos.data_ptr(), int(B), D, int(Lcap),
+                                            lda, int(T), dtype_code(hist.dtype), _backend.stream(k.device)))
+
+
+def decode_post_block(part, hist, fb, x0, z, pos, Lcap):
+    """z (B, T, D) = round(round(sum of the partials + fb hist[:, :, t0 + i]) * x0); then pos = t0 + T"""
+    _require_gpu(z, "z")
+    _, D, lda = _hist(hist)
+    B, T, _ = z.shape
+    _block_out(x0, z, B, T, D, hist)
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post_block(part.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
+                                            z.data_ptr(), pos.data_ptr(), B, D, int(Lcap), lda, T, dtype_code(hist.dtype),
+                                            _backend.stream(z.device)))
+
+
+def decode_pre_block_fan(x3, bin_, w, b, tail, hist_r, x0, pos, Lcap, S):
+    """decode_pre_block with the new columns written to hist_r[:, :, t0 - S ...]"""
+    _require_gpu(x3, "x")
+    Bcap, D, ldr = _hist(hist_r)
+    B, T, ldx = _block_x(x3, hist_r)
+    _block_out(x0, None, B, T, D, hist_r)
+    with _backend.guard(x3.device):
+        check(lib().hyena_decode_pre_block_fan(x3.data_ptr(), ldx, None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                               tail.data_ptr(), hist_r.data_ptr(), x0.data_ptr(), pos.data_ptr(), B, Bcap, D, int(Lcap), int(S),
+                                               ldr, T, dtype_code(x3.dtype), _backend.stream(x3.device)))
+
+
+def decode_conv_block_fan(k, hist_s, hist_r, part, pos, B, fan, T, Lcap, S):
+    """decode_conv_block with the chunks below S computed once per group, from hist_s, into part[chunk][g fan]"""
+    _require_gpu(k, "k")
+    _, D, ldr = _hist(hist_r)
+    lds = 0
+    if hist_s is not None:
+        G, Ds, lds = _hist(hist_s)
+        assert Ds == D and hist_s.dtype == hist_r.dtype and G * int(fan) >= int(B)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv_block_fan(k.data_ptr(), k.stride(0), None if hist_s is None else hist_s.data_ptr(), hist_r.data_ptr(),
+                                                part.data_ptr(), pos.data_ptr(), int(B), int(fan), D, int(Lcap), int(S), lds, ldr, int(T),
+                                                dtype_code(hist_r.dtype), _backend.stream(k.device)))
+
+
+def decode_post_block_fan(part, hist_r, fb, x0, z, pos, fan, Lcap, S):
+    """decode_post_block with the partials of the chunks below S read from the group's slot; then pos = t0 + T"""
+    _require_gpu(z, "z")
+    _, D, ldr = _hist(hist_r)
+    B, T, _ = z.shape
+    _block_out(x0, z, B, T, D, hist_r)
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post_block_fan(part.data_ptr(), hist_r.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
+                                                z.data_ptr(), pos.data_ptr(), B, int(fan), D, int(Lcap), int(S), ldr, T,
+                                                dtype_code(hist_r.dtype), _backend.stream(z.device)))
 
 
 # ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------

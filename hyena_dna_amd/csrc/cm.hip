@@ -145,7 +145,15 @@ DecFanArgs dec_fan_args(const void* vgs, int fan, int S, int lds) {
     a.vgs = vgs; a.fan = fan; a.S = S; a.lds = lds;
     return a;
 }
-#define HY_DEC_DISPATCH(kernel, grid, threads, smem)                                                                  \
+bool dec_block_T_ok(int T) { return T >= 1 && T <= DEC_TMAX; }
+DecBlockArgs dec_block_args(const void* vgs, int fan, int S, int lds, int T) {
+    DecBlockArgs a;
+    static_cast<DecFanArgs&>(a) = dec_fan_args(vgs, fan, S, lds);
+    a.T = T;
+    return a;
+}
+static_assert(DEC_TMAX == HYENA_DECODE_TMAX, "the header's block limit");
+#define HY_DEC_DISPATCH(kernel, grid, threads, smem)                                                                 \
     do {                                                                                                              \
         switch (dtype) {                                                                                              \
             case HYENA_F32: HY_LAUNCH((kernel<DT_F32>), grid, dim3(threads), smem, stream, a); break;                 \
@@ -268,6 +276,69 @@ int hyena_decode_post_fan(const float* part, const void* vgr, const float* fb, c
     a.B = B; a.D = D; a.Lcap = Lcap; a.lda = ldr;
     HY_DEC_DISPATCH(decode_post_fan_kernel, dim3(1), DEC_POST_THREADS, 0);
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+// ---- block step: T positions per call (decode_*_block_kernel; one set of kernels, the plain layout is S = 0, fan = 1) -----------------------
+size_t hyena_decode_block_partial_floats(int B, int D, int Lcap, int T) {
+    if (B < 1 || D < 1 || Lcap < 1 || Lcap > DEC_MAX_L || !dec_block_T_ok(T)) return 0;
+    return (size_t)dec_chunks(Lcap) * B * T * D;
+}
+
+int hyena_decode_pre_block_fan(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vgr, float* x0,
+                               const int* pos, int B, int Bcap, int D, int Lcap, int S, int ldr, int T, int dtype, void* stream) {
+    if (!dec_block_T_ok(T) || x == nullptr || w == nullptr || b == nullptr || tail == nullptr || x0 == nullptr || pos == nullptr ||
+        !dec_fan_ok(false, nullptr, vgr, B, 1, D, Lcap, S, 0, ldr, dtype) || Bcap < B || ldx < 3 * D || (long)Bcap * D > (1L << 30))
+        return HYENA_ERR_BAD_ARG;
+    DecBlockArgs a = dec_block_args(nullptr, 1, S, 0, T);
+    a.x = x; a.bin = bin; a.w = w; a.b = b; a.tail = tail; a.vg = vgr; a.x0 = x0; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Bcap = Bcap; a.Lcap = Lcap; a.ldx = ldx; a.lda = ldr;
+    HY_DEC_DISPATCH(decode_pre_block_kernel, dim3((B * D + DEC_THREADS - 1) / DEC_THREADS), DEC_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_conv_block_fan(const float* k, int ldk, const void* vgs, const void* vgr, float* part, const int* pos, int B, int fan, int D,
+                                int Lcap, int S, int lds, int ldr, int T, int dtype, void* stream) {
+    if (!dec_block_T_ok(T) || k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || pos == nullptr ||
+        !dec_fan_ok(true, vgs, vgr, B, fan, D, Lcap, S, lds, ldr, dtype) || D > 65535)
+        return HYENA_ERR_BAD_ARG;
+    DecBlockArgs a = dec_block_args(vgs, fan, S, lds, T);
+    a.k = k; a.vg = const_cast<void*>(vgr); a.part = part; a.pos = const_cast<int*>(pos);
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = ldr; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_conv_block_kernel, dim3(dec_chunks(Lcap), D), DEC_THREADS, (DEC_KLDS_BLOCK + DEC_RED_BLOCK) * sizeof(float));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_post_block_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
+                                int Lcap, int S, int ldr, int T, int dtype, void* stream) {
+    if (!dec_block_T_ok(T) || part == nullptr || x0 == nullptr || z == nullptr || pos == nullptr ||
+        !dec_fan_ok(false, nullptr, vgr, B, fan, D, Lcap, S, 0, ldr, dtype) || (long)B * D > (1L << 30) / DEC_TMAX)
+        return HYENA_ERR_BAD_ARG;
+    DecBlockArgs a = dec_block_args(nullptr, fan, S, 0, T);
+    a.part = const_cast<float*>(part); a.vg = const_cast<void*>(vgr); a.fb = fb; a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = ldr;
+    HY_DEC_DISPATCH(decode_post_block_kernel, dim3((unsigned)(((size_t)B * T * D + DEC_THREADS - 1) / DEC_THREADS)), DEC_THREADS, 0);
+    if (hy_launch_error()) return HYENA_ERR_LAUNCH;
+    HY_LAUNCH(decode_advance_block_kernel, dim3(1), dim3(64), 0, stream, pos, T, S, Lcap);   // after every read of the position
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+// the plain cache: nothing shared (S = 0, fan = 1), the history (Bcap, D, lda) with lda >= Lcap
+int hyena_decode_pre_block(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vg, float* x0,
+                           const int* pos, int B, int Bcap, int D, int Lcap, int lda, int T, int dtype, void* stream) {
+    if (!dec_hist_ok(vg, B, D, Lcap, lda, dtype)) return HYENA_ERR_BAD_ARG;
+    return hyena_decode_pre_block_fan(x, ldx, bin, w, b, tail, vg, x0, pos, B, Bcap, D, Lcap, 0, lda, T, dtype, stream);
+}
+
+int hyena_decode_conv_block(const float* k, int ldk, const void* vg, float* part, const int* pos, int B, int D, int Lcap, int lda, int T,
+                            int dtype, void* stream) {
+    if (!dec_hist_ok(vg, B, D, Lcap, lda, dtype)) return HYENA_ERR_BAD_ARG;
+    return hyena_decode_conv_block_fan(k, ldk, nullptr, vg, part, pos, B, 1, D, Lcap, 0, 0, lda, T, dtype, stream);
+}
+
+int hyena_decode_post_block(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
+                            int lda, int T, int dtype, void* stream) {
+    if (!dec_hist_ok(vg, B, D, Lcap, lda, dtype)) return HYENA_ERR_BAD_ARG;
+    return hyena_decode_post_block_fan(part, vg, fb, x0, z, pos, B, 1, D, Lcap, 0, lda, T, dtype, stream);
 }
 
 // ---- token sampling (decode_sample_kernel): one wavefront per logit row -------------------------------------------------------------------

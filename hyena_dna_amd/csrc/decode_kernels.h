@@ -11,6 +11,7 @@
 //   decode_post  the partials summed in chunk order, + fb vg_t, rounded to the I/O type where the forward rounds the convolution's output,
 //                times x0_t with cm_post_fwd's arithmetic -> z_t; then the position advances
 // The position t lives in device memory and all three kernels read it there: one captured graph serves every position.
+// Variants further down: one position per row (_rows), n continuations of one prompt (_fan), and T known positions per call (_block).
 //
 // The two streams of decode_conv run in opposite directions (vg forward in s, k backward), and the k stream is misaligned by t mod 4 words
 // relative to the vg stream.  The history is the operand that scales with B, so ITS loads stay aligned 16-byte vectors (8 elements per lane at
@@ -418,6 +419,224 @@ __global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_fan_kernel(DecFa
     }
     __syncthreads();
     if (threadIdx.x == 0 && valid) a.pos[0] = t + 1;
+}
+
+// ---- block step: T known positions appended in one pass (C ABI: hyena_decode_*_block and *_block_fan) -------------------------------------
+// All B rows advance from t0 = *pos to t0 + T, 1 <= T <= DEC_TMAX.  The T outputs of a (row, channel) read the same history and a filter
+// window only T - 1 taps longer, so the history is streamed ONCE for the block: a lane keeps its DEC_NV 8-element history vectors in
+// registers and runs T accumulators over them, DEC_TT (or DEC_TR for the remainder) at a time.  One set of kernels serves the plain cache
+// (S = 0, fan = 1: nothing is shared) and the fan-out layout of DecFanArgs.
+//   x (B, T, 3D): element (b, i, c) at (b T + i) ldx + c;   x0, z (B, T, D);   part [chunk][B][T][D] (the slot rule of the fan kernels:
+//   a chunk below S writes and reads slot b = g fan only)
+// Bit for bit what T single-position steps leave (z, x0, the history columns, tail, pos), because every output keeps its summation:
+//   - output i of a lane is its own FMA chain over (vector v, element e) in that order, starting from 0.  The single-position kernel
+//     skips a vector that starts past t and selects a zero tap past t inside a vector; here those taps are zeros of the staged window
+//     (k has no negative index), and fma(0, x, acc) == acc for finite x and any acc this chain can hold (it never holds -0: it starts at
+//     +0, and x + y is -0 only when both are).  Vectors that start past t0 + T - 1 are skipped.  So the history columns a block touches
+//     past an output's own position -- the block's later columns and up to 7 columns of over-read -- must be finite, as today.
+//   - then cm_wave_sum, (r0 + r1) + (r2 + r3) over the four wavefronts, and the chunks in order in decode_post_block.
+// Filter window in LDS: ks[m] = k[c, jlo + m], jlo = t0 - s0 - DEC_CHUNK + 1, m in [0, DEC_CHUNK + DEC_TMAX), zero where jlo + m is negative
+// or past t0 + T - 1 - s0.  The tap of (output i, position s = s0 + 8 q + e) is k[t0 + i - s] = ks[(DEC_CHUNK - 8 - 8 q + i0) + (i - i0) - e + 7]:
+// a lane's window for a tile of outputs [i0, i0 + TT) is the TT + 7 floats from an index that is a multiple of 4 (i0 is), read as aligned
+// 16-byte LDS vectors into registers once per (vector, tile) and slid over the 8 elements -- (TT + 8) / 4 LDS reads for 8 TT FMAs.  The
+// staging itself is dword loads (coalesced; jlo has any alignment), once per workgroup for all rows.
+enum { DEC_TMAX = 64, DEC_TT = 16, DEC_TR = 4, DEC_PRE_J = 8, DEC_KLDS_BLOCK = DEC_CHUNK + DEC_TMAX, DEC_RED_BLOCK = 2 * DEC_TT * 4 };
+
+struct DecBlockArgs : DecFanArgs {
+    int T;
+};
+
+__device__ __forceinline__ bool dec_block_valid(const DecBlockArgs& a, int t0) { return t0 >= a.S && t0 <= a.Lcap - a.T; }
+
+// one thread per (b, d), the T positions in order: grid ceil(B D / DEC_THREADS)
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_pre_block_kernel(DecBlockArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int i = (int)(blockIdx.x * DEC_THREADS + threadIdx.x);
+    const int t0 = a.pos[0];
+    if (i >= a.B * a.D || !dec_block_valid(a, t0)) return;
+    const int b = i / a.D, d = i % a.D;
+    const elem_t* x = reinterpret_cast<const elem_t*>(a.x) + (size_t)b * a.T * a.ldx;
+    elem_t* vg = reinterpret_cast<elem_t*>(a.vg) + ((size_t)b * a.D + d) * a.lda + (t0 - a.S);
+    float* x0 = a.x0 + (size_t)b * a.T * a.D + d;
+    float xm2[3], xm1[3], w[3][3], bsc[3], bin[3];
+    HY_UNROLL
+    for (int g = 0; g < 3; ++g) {
+        const int c = g * a.D + d;
+        const float* tl = a.tail + ((size_t)c * a.Bcap + b) * 2;
+        xm2[g] = tl[0];
+        xm1[g] = tl[1];
+        w[g][0] = a.w[c * 3]; w[g][1] = a.w[c * 3 + 1]; w[g][2] = a.w[c * 3 + 2];
+        bsc[g] = a.b[c];
+        bin[g] = a.bin != nullptr ? a.bin[c] : 0.f;
+    }
+    for (int j0 = 0; j0 < a.T; j0 += DEC_PRE_J) {
+        float xin[DEC_PRE_J][3];                                         // the loads of DEC_PRE_J positions in flight before the first store
+        HY_UNROLL
+        for (int jj = 0; jj < DEC_PRE_J; ++jj) {
+            const int j = j0 + jj < a.T ? j0 + jj : a.T - 1;
+            HY_UNROLL
+            for (int g = 0; g < 3; ++g) xin[jj][g] = Elem<DT>::dec(x[(size_t)j * a.ldx + g * a.D + d]);
+        }
+        HY_UNROLL
+        for (int jj = 0; jj < DEC_PRE_J; ++jj) {
+            const int j = j0 + jj;
+            if (j < a.T) {
+                float o[3];
+                HY_UNROLL
+                for (int g = 0; g < 3; ++g) {
+                    const float xn = xin[jj][g];
+                    o[g] = dec_sc(xm2[g], xm1[g], xn, t0 + j, w[g][0], w[g][1], w[g][2], bsc[g], bin[g]);
+                    xm2[g] = xm1[g];
+                    xm1[g] = xn;
+                }
+                float p = o[1] * o[2];                                   // one fp32 product, then one conversion (decode_pre_kernel)
+#if !defined(HIPEMU)
+                asm volatile("" : "+v"(p));
+#endif
+                vg[j] = Elem<DT>::cvt(p);
+                x0[(size_t)j * a.D] = o[0];
+            }
+        }
+    }
+    HY_UNROLL
+    for (int g = 0; g < 3; ++g) {
+        float* tl = a.tail + ((size_t)(g * a.D + d) * a.Bcap + b) * 2;
+        tl[0] = xm2[g];
+        tl[1] = xm1[g];
+    }
+}
+
+// TT outputs [i0, i0 + TT) of one row over the lane's history vectors: acc[ii] is output i0 + ii's FMA chain over (v, e)
+template <int TT>
+__device__ __forceinline__ void dec_block_tile(const float (&x)[DEC_NV][DEC_V], const bool (&live)[DEC_NV], const HY_LDS float* ks, int tid,
+                                               int i0, float (&acc)[TT]) {
+    constexpr int NW = (TT + 7 + 3) / 4 * 4;
+    HY_UNROLL
+    for (int ii = 0; ii < TT; ++ii) acc[ii] = 0.f;
+    HY_UNROLL
+    for (int v = 0; v < DEC_NV; ++v) {
+        if (live[v]) {
+            const int m0 = DEC_CHUNK - DEC_V - (v * DEC_THREADS + tid) * DEC_V + i0;   // a multiple of 4: aligned 16-byte LDS reads
+            float w[NW];
+            HY_UNROLL
+            for (int q = 0; q < NW / 4; ++q) {
+#if defined(HIPEMU)
+                __builtin_memcpy(w + 4 * q, ks + m0 + 4 * q, 16);
+#else
+                typedef float dec_f4 __attribute__((ext_vector_type(4)));
+                const dec_f4 r = *reinterpret_cast<const HY_LDS dec_f4*>(ks + m0 + 4 * q);
+                w[4 * q] = r.x; w[4 * q + 1] = r.y; w[4 * q + 2] = r.z; w[4 * q + 3] = r.w;
+#endif
+            }
+            HY_UNROLL
+            for (int e = 0; e < DEC_V; ++e) {
+                HY_UNROLL
+                for (int ii = 0; ii < TT; ++ii) acc[ii] = __builtin_fmaf(w[ii - e + 7], x[v][e], acc[ii]);
+            }
+        }
+    }
+}
+
+// wavefront sums of the tile's outputs -> red (one parity) -> part[chunk][slot][i0 + ii][c]; one barrier
+template <int TT>
+__device__ __forceinline__ void dec_block_reduce(float (&acc)[TT], HY_LDS float* rb, int tid, int i0, int T, float* part, int D) {
+    HY_UNROLL
+    for (int ii = 0; ii < TT; ++ii) acc[ii] = cm_wave_sum(acc[ii]);
+    if ((tid & 63) == 0) {
+        HY_UNROLL
+        for (int ii = 0; ii < TT; ++ii) rb[ii * 4 + (tid >> 6)] = acc[ii];
+    }
+    __syncthreads();
+    if (tid < TT && i0 + tid < T) part[(size_t)(i0 + tid) * D] = (rb[tid * 4] + rb[tid * 4 + 1]) + (rb[tid * 4 + 2] + rb[tid * 4 + 3]);
+}
+
+// grid (nchunks, D) as decode_conv_fan_kernel, the same split between shared and row history.  Every branch around a barrier is taken on
+// pos[0], T, S and blockIdx: uniform across the workgroup; one barrier per (row, tile).  A chunk that starts inside the block
+// (t0 < s0 <= t0 + T - 1) also writes the (zero) partials of the outputs before s0, which decode_post_block does not read.
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_conv_block_kernel(DecBlockArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS_BLOCK;                             // [2][DEC_TT][4]: wavefront sums, alternating by the parity of the trip
+    const int t0 = a.pos[0];
+    const int chunk = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, T = a.T;
+    const int s0 = chunk * DEC_CHUNK;
+    if (!dec_block_valid(a, t0) || s0 > t0 + T - 1) return;
+    const int tmax = t0 + T - 1;
+    const int jlo = t0 - s0 - DEC_CHUNK + 1, jhi = tmax - s0;
+    const float* krow = a.k + (size_t)c * a.ldk;
+    for (int m = tid; m < DEC_KLDS_BLOCK; m += DEC_THREADS) {
+        const int j = jlo + m;
+        const bool ok = j >= 0 && j <= jhi;
+        const float kv = krow[ok ? j : 0];
+        ks[m] = ok ? kv : 0.f;
+    }
+    __syncthreads();
+    const bool shared = s0 < a.S;                                        // S is a multiple of DEC_CHUNK: the whole chunk lies on one side
+    const int nrows = shared ? a.B / a.fan : a.B;
+    const void* src = shared ? a.vgs : a.vg;
+    const int ld = shared ? a.lds : a.lda;
+    const int off = shared ? 0 : a.S;                                    // the tensor's column of history position s: s - off
+    bool live[DEC_NV];
+    HY_UNROLL
+    for (int v = 0; v < DEC_NV; ++v) live[v] = s0 + (v * DEC_THREADS + tid) * DEC_V <= tmax;
+    int trip = 0;
+    for (int r = 0; r < nrows; ++r) {
+        const char* row = cm_row(src, (size_t)r * a.D + c, ld, ES);
+        float x[DEC_NV][DEC_V];
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            HY_UNROLL
+            for (int e = 0; e < DEC_V; ++e) x[v][e] = 0.f;
+            if (live[v]) {                                                // (s - off + DEC_V <= ld: 8-aligned rows; s <= tmax < Lcap)
+                // aligned 16-byte loads, ONCE per block step; positions past an output's own meet a zero tap (finite history)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)(s - off) * ES, 16), sizeof(raw));
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) x[v][e] = Elem<DT>::dec(raw[e]);
+            }
+        }
+        const int slot = shared ? r * a.fan : r;
+        float* part = a.part + (((size_t)chunk * a.B + slot) * T) * a.D + c;
+        int i0 = 0;
+        for (; T - i0 > 3 * DEC_TR; i0 += DEC_TT) {                       // whole tiles, and a remainder of more than three small ones
+            float acc[DEC_TT];
+            dec_block_tile<DEC_TT>(x, live, ks, tid, i0, acc);
+            dec_block_reduce<DEC_TT>(acc, red + DEC_TT * 4 * (trip++ & 1), tid, i0, T, part, a.D);
+        }
+        for (; i0 < T; i0 += DEC_TR) {
+            float acc[DEC_TR];
+            dec_block_tile<DEC_TR>(x, live, ks, tid, i0, acc);
+            dec_block_reduce<DEC_TR>(acc, red + DEC_TT * 4 * (trip++ & 1), tid, i0, T, part, a.D);
+        }
+    }
+}
+
+// one thread per (b, i, d): grid ceil(B T D / DEC_THREADS).  Nothing here writes pos: decode_advance_block_kernel follows on the stream.
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_post_block_kernel(DecBlockArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int t0 = a.pos[0];
+    const size_t idx = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+    if (idx >= (size_t)a.B * a.T * a.D || !dec_block_valid(a, t0)) return;
+    const int d = (int)(idx % a.D), i = (int)(idx / a.D % a.T), b = (int)(idx / a.D / a.T);
+    const int t = t0 + i;
+    const int nc = t / DEC_CHUNK + 1, ns = a.S / DEC_CHUNK, bs = b / a.fan * a.fan;
+    float y = 0.f;
+    for (int ch = 0; ch < nc; ++ch) y += a.part[(((size_t)ch * a.B + (ch < ns ? bs : b)) * a.T + i) * a.D + d];
+    const float u = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.vg)[((size_t)b * a.D + d) * a.lda + (t - a.S)]);
+    if (a.fb != nullptr) y = __builtin_fmaf(u, a.fb[d], y);
+    const float yr = Elem<DT>::dec(Elem<DT>::cvt(y));                     // the forward's convolution output is stored in the I/O type
+    reinterpret_cast<elem_t*>(a.z)[idx] = Elem<DT>::cvt(yr * a.x0[idx]);  // cm_post_fwd: y * c0, rounded once
+}
+
+// one thread, after decode_post_block_kernel on the same stream: the position advances by T
+__global__ void __launch_bounds__(64) decode_advance_block_kernel(int* pos, int T, int S, int Lcap) {
+    const int t0 = pos[0];
+    if (threadIdx.x == 0 && blockIdx.x == 0 && t0 >= S && t0 <= Lcap - T) pos[0] = t0 + T;
 }
 
 // ---- token sampling: the last node of the per-token graph (C ABI: hyena_decode_sample) ---------------------------------------------------

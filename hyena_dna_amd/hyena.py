@@ -467,7 +467,9 @@ class HyenaOperator(nn.Module):
 
     def _forward_cached(self, u, ip):
         """forward(u, inference_params=ip): the prefill (ip.seqlen_offset == 0: the plain forward over the prompt, bit for bit, which also fills the
-        cache) or one step (u (B, 1, D), ip.seqlen_offset > 0: position seqlen_offset of every sequence, three kernels between the GEMVs)."""
+        cache), one step (u (B, 1, D), ip.seqlen_offset > 0: position seqlen_offset of every sequence, three kernels between the GEMVs), or
+        an append (ip.allow_append, u (B, l > 1, D) at ip.seqlen_offset > 0: positions seqlen_offset ... seqlen_offset + l - 1, block steps of at most 64
+        positions that stream the history once each and leave the cache bit for bit as l single steps do)."""
         from .inference import check_decodable
         check_decodable(self)
         st = ip.key_value_memory_dict.get(self._decode_key())
@@ -489,9 +491,28 @@ class HyenaOperator(nn.Module):
             if xT.dtype != st.dtype:
                 raise ValueError(f"the prefill runs in {xT.dtype}, the decode cache was built for {st.dtype}")
             st.store_prefill(xT, vg, l, lengths=getattr(ip, "lengths_per_sample", None))
+        elif l > 1 and not getattr(ip, "allow_append", False):
+            raise ValueError(f"a decode step takes one position per sequence (got {l}); prefill with seqlen_offset = 0, or set "
+                             f"inference_params.allow_append = True to append the {l} known positions to the cache")
+        elif l > 1:
+            # append l known positions: block steps of at most 64, each streaming the history once (csrc/decode_kernels.h decode_*_block)
+            from . import _lib
+            if off + l > st.L:
+                raise ValueError(f"positions {off} ... {off + l - 1} reach past the decode cache's max_seqlen = {st.L} "
+                                 f"(offset {off} + {l} positions)")
+            x = hyena_linear(u, self.in_proj.weight, None)                   # (B, l, 3D)
+            if x.dtype != st.dtype:
+                raise ValueError(f"the step runs in {x.dtype}, the decode cache was built for {st.dtype}")
+            if l <= _lib.DECODE_TMAX:
+                z = st.step_block(x)
+            else:                                                            # (step_block's z is the cache's scratch: the next tile overwrites it)
+                z = torch.empty(B, l, self.d_model, dtype=st.dtype, device=u.device)
+                for i in range(0, l, _lib.DECODE_TMAX):
+                    z[:, i:i + _lib.DECODE_TMAX].copy_(st.step_block(x[:, i:i + _lib.DECODE_TMAX]))
+            y = hyena_linear(z, self.out_proj.weight, self.out_proj.bias)
         else:
             if l != 1:
-                raise ValueError(f"a decode step takes one position per sequence (got {l}); prefill with seqlen_offset = 0")
+                raise ValueError(f"a decode step takes at least one position per sequence (got {l})")
             if off >= st.L:
                 raise ValueError(f"position {off} is past the decode cache's max_seqlen = {st.L}")
             x = hyena_linear(u, self.in_proj.weight, None)                   # (B, 1, 3D): the forward's 16-bit weight shadows / autocast

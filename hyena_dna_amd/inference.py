@@ -6,7 +6,8 @@ dot product over the history of the convolution's input ``vg = v * x1``.  ``Hyen
 ``filter_dl(max_seqlen)``, the history, the last two in_proj outputs the 3-tap short convolution still needs, the position (in device
 memory: one captured graph serves every position; one int for the batch, or one per row after a right-padded prefill with
 ``InferenceParams.lengths_per_sample``) and the step's small buffers -- and ``HyenaOperator.forward(u, inference_params=ip)``
-fills it with a prefill (``ip.seqlen_offset == 0``) and advances it by one position per call afterwards (csrc/decode_kernels.h).
+fills it with a prefill (``ip.seqlen_offset == 0``) and advances it afterwards by one position per call, or by the T known positions of a
+``(B, T, D)`` input in block steps that stream the history once per 64 positions (``step_block``; csrc/decode_kernels.h).
 """
 import torch
 
@@ -20,15 +21,22 @@ class InferenceParams:
     older name), ``batch_size_offset``, ``key_value_memory_dict`` (layer key -> that layer's cache), ``lengths_per_sample``.
 
     ``lengths_per_sample``: None, or the device int32 (B,) tensor of the prompts' own lengths when the prefill batch is right-padded.  The
-    prefill hands it to every layer's cache (``HyenaDecodeState.store_prefill``), which from then on keeps one position per row."""
+    prefill hands it to every layer's cache (``HyenaDecodeState.store_prefill``), which from then on keeps one position per row.
 
-    def __init__(self, max_seqlen, max_batch_size, seqlen_offset=0, batch_size_offset=0, key_value_memory_dict=None, lengths_per_sample=None):
+    ``allow_append`` (this package's addition; an attribute set on flash_attn's own object serves as well): with it a call at
+    ``seqlen_offset > 0`` with SEVERAL positions per sequence appends them all to the cache in block steps
+    (``HyenaDecodeState.step_block``).  Without it such a call stays the error it has always been: a decode loop that hands the model more
+    than its one new token by mistake must not move the cache."""
+
+    def __init__(self, max_seqlen, max_batch_size, seqlen_offset=0, batch_size_offset=0, key_value_memory_dict=None, lengths_per_sample=None,
+                 allow_append=False):
         self.max_seqlen = max_seqlen
         self.max_batch_size = max_batch_size
         self.seqlen_offset = seqlen_offset
         self.batch_size_offset = batch_size_offset
         self.key_value_memory_dict = {} if key_value_memory_dict is None else key_value_memory_dict
         self.lengths_per_sample = lengths_per_sample
+        self.allow_append = allow_append
 
     @property
     def sequence_len_offset(self):
@@ -132,6 +140,7 @@ class HyenaDecodeState:
         self.x0 = torch.empty(self.B, D, dtype=torch.float32, device=dev)
         self.z = torch.empty(self.B, D, dtype=self.dtype, device=dev)
         self.part = _lib.decode_partials(self.B, D, L, dev)
+        self.block_buf = None                                                         # step_block's part / x0 / z: allocated on first use
 
     def store_prefill(self, xT, vg, P, lengths=None):
         """after the prefill forward over P positions: its convolution input vg (B, D, P) and the last two in_proj outputs of xT (3D, B, P).
@@ -198,6 +207,40 @@ class HyenaDecodeState:
         _lib.decode_pre(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L)
         _lib.decode_conv(self.k, self.hist, self.part, self.pos, B, self.L)
         _lib.decode_post(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.L)
+        return z
+
+    def _block_buffers(self, B, T):
+        """the block step's scratch for (B, T): allocated on first use, grown when a larger block comes, never shrunk"""
+        need = {"x0": B * T * self.D, "z": B * T * self.D,
+                "part": int(_lib.lib().hyena_decode_block_partial_floats(B, self.D, self.L, T))}
+        if self.block_buf is None or any(self.block_buf[n].numel() < need[n] for n in need):
+            dev = self.hist.device
+            have = {n: 0 if self.block_buf is None else self.block_buf[n].numel() for n in need}
+            self.block_buf = {n: torch.empty(max(need[n], have[n]), dtype=self.dtype if n == "z" else torch.float32, device=dev) for n in need}
+        buf = self.block_buf
+        return buf["part"], buf["x0"][:need["x0"]].view(B, T, self.D), buf["z"][:need["z"]].view(B, T, self.D)
+
+    def step_block(self, x3):
+        """x3 (B, T, 3D), 1 <= T <= 64: in_proj output of T known positions without bias -> z (B, T, D) for out_proj; the position advances
+        by T.  Three kernels that stream the history once for the T positions; the results (z, history, tail, position) equal those of T
+        calls of ``step`` bit for bit.  ``z`` is a view of the cache's scratch: the next block step overwrites it."""
+        if self.ragged:
+            raise NotImplementedError("a decode cache in ragged mode (prefill with lengths) has no block step: one position per row and call")
+        B, T, _ = x3.shape
+        if not 1 <= T <= _lib.DECODE_TMAX:
+            raise ValueError(f"a block step takes 1 ... {_lib.DECODE_TMAX} positions (got {T})")
+        x3 = x3.contiguous()
+        part, x0, z = self._block_buffers(B, T)
+        if self.fan > 1:
+            if B != self.B:
+                raise ValueError(f"a step of a decode cache with fan = {self.fan} takes all {self.B} rows (got {B})")
+            _lib.decode_pre_block_fan(x3, self.bin, self.w, self.b, self.tail, self.hist, x0, self.pos, self.L, self.S)
+            _lib.decode_conv_block_fan(self.k, self.hist_shared, self.hist, part, self.pos, B, self.fan, T, self.L, self.S)
+            _lib.decode_post_block_fan(part, self.hist, self.fb, x0, z, self.pos, self.fan, self.L, self.S)
+            return z
+        _lib.decode_pre_block(x3, self.bin, self.w, self.b, self.tail, self.hist, x0, self.pos, self.L)
+        _lib.decode_conv_block(self.k, self.hist, part, self.pos, B, T, self.L)
+        _lib.decode_post_block(part, self.hist, self.fb, x0, z, self.pos, self.L)
         return z
 
 

@@ -795,7 +795,9 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         # (the head through projection.hyena_linear: its weight gradient contracts 16 x 256 outputs over 10^6 tokens, which the GEMM library
         # runs on 16 workgroups -- 1.19 ms per step at 2^20 tokens, profiles/r4y_model_stats.csv -- and the split-K form does not)
         if inference_params is not None:
-            # incremental decoding: the prompt as it is (padding would put positions into the cache), then one position per call
+            # incremental decoding: the prompt as it is (padding would put positions into the cache), then one position per call -- or
+            # with inference_params.allow_append (B, T) known tokens at an offset, which every layer appends in block steps
+            # (HyenaOperator._forward_cached)
             emb = self.backbone.embeddings
             if position_ids is None and emb.max_position_embeddings > 0:
                 off = int(inference_params.seqlen_offset)
@@ -811,6 +813,50 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         if Lp != L:
             lm_logits = lm_logits[:, :L]                 # (a view: the pad positions' logits reach nobody -> zero gradients)
         return namedtuple("CausalLMOutput", ["logits"])(logits=lm_logits), None
+
+    @torch.no_grad()
+    def score_continuations(self, context_ids, continuations, vocab_size=None, return_logits=False):
+        """log-likelihood of n candidate continuations of T tokens after each of G contexts of P tokens:
+        ``context_ids`` (G, P), ``continuations`` (G, n, T) -> ``logprobs`` (G, n, T) fp32 with
+        ``logprobs[g, j, i] = log p(continuations[g, j, i] | context_ids[g], continuations[g, j, :i])``.
+
+        One prefill over the G contexts fills a decode cache laid out for n rows per context (``fan=n``: the history below
+        ``(P // 8192) * 8192`` is kept once per context); token 0 of every candidate is scored from its context's last logits; one cached
+        forward over ``continuations[..., :-1]`` as (G n, T - 1) then appends the known tokens in block steps of at most 64 positions, each
+        streaming the history once (``HyenaDecodeState.step_block``).  ``vocab_size``: the softmax runs over the first ``vocab_size`` logit
+        columns (the padded vocabulary excluded; None: all).  ``return_logits=True``: also the (G, n, T, V) fp32 logits."""
+        if context_ids.dim() != 2 or continuations.dim() != 3 or continuations.shape[0] != context_ids.shape[0]:
+            raise ValueError(f"score_continuations takes context_ids (G, P) and continuations (G, n, T) (got {tuple(context_ids.shape)} and "
+                             f"{tuple(continuations.shape)})")
+        (G, P), (_, n, T) = context_ids.shape, continuations.shape
+        if G < 1 or P < 1 or n < 1 or T < 1:
+            raise ValueError(f"score_continuations needs at least one context, context token, candidate and continuation token "
+                             f"(got G = {G}, P = {P}, n = {n}, T = {T})")
+        from . import _lib
+        from .inference import InferenceParams
+        limit = min([getattr(m, "l_max", _lib.MAX_L) for m in self._mixers()] + [_lib.MAX_L])
+        if P + T - 1 > limit:
+            raise ValueError(f"context ({P}) + continuation ({T}) - 1 = {P + T - 1} positions do not fit the decode cache's limit of {limit}")
+        if continuations.dtype != context_ids.dtype or continuations.device != context_ids.device:
+            raise ValueError("context_ids and continuations must have the same dtype and device")
+        Vall = self.lm_head.weight.shape[0]
+        V = Vall if vocab_size is None else int(vocab_size)
+        if not 1 <= V <= Vall:
+            raise ValueError(f"vocab_size={vocab_size}: the model has {Vall} logit columns")
+        if int(continuations.min()) < 0 or int(continuations.max()) >= V:
+            raise ValueError(f"continuations hold token ids outside [0, {V})")
+        B = G * n
+        ip = InferenceParams(max_seqlen=P + T - 1, max_batch_size=B, allow_append=True)
+        ip.key_value_memory_dict = self.allocate_inference_cache(B, P + T - 1, **({} if n == 1 else dict(fan=n, prompt_len=P)))
+        first = self(context_ids, inference_params=ip)[0].logits[:, -1:].float()                     # (G, 1, V)
+        logits = first[:, None].expand(G, n, 1, first.shape[-1])
+        if T > 1:
+            ip.seqlen_offset = P
+            rest = self(continuations[:, :, :-1].reshape(B, T - 1), inference_params=ip)[0].logits.float()
+            logits = torch.cat([logits, rest.view(G, n, T - 1, -1)], dim=2)
+        logits = logits.contiguous()                                                                  # (G, n, T, V)
+        logprobs = torch.log_softmax(logits[..., :V], dim=-1).gather(-1, continuations.long().unsqueeze(-1)).squeeze(-1)
+        return (logprobs, logits) if return_logits else logprobs
 
     def loss(self, input_ids, targets, ignore_index=-100):
         """next-token cross entropy (src/tasks/metrics.py cross_entropy over the flattened logits), logits in fp32"""

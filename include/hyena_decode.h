@@ -1,5 +1,6 @@
-/* hyena_decode.h -- C ABI of the incremental (one position per call) Hyena operator step (same library, libhyena_fftconv.so;
- * kernels in hyena_dna_amd/csrc/decode_kernels.h).
+/* hyena_decode.h -- C ABI of the incremental Hyena operator step: one position per call, or a block of up to HYENA_DECODE_TMAX known
+ * positions per call (the last section of this comment) (same library, libhyena_fftconv.so; kernels in
+ * hyena_dna_amd/csrc/decode_kernels.h).
  *
  * Order 2, one head, one block, inner factor 1, short_filter_order 3 (the fused route of HyenaOperator).  One call of each entry point
  * advances ALL B sequences by one position t; t is read from device memory (`pos`, one int) by every kernel and advanced by
@@ -37,10 +38,28 @@
  * row for the chunks from S on; hyena_decode_post_fan sums row b's partials in chunk order, taking chunk < S / 8192 from slot g fan.  On
  * the batch whose B rows hold the replicated history the single-position entry points give the same z, x0, tail, history column and
  * position, bit for bit.  A position outside [S, Lcap) makes the kernels do nothing.  Bad arguments -- those above, and S not a multiple of
- * 8192, S > Lcap, fan < 1, B not a multiple of fan, a misaligned pointer or pitch -- return HYENA_ERR_BAD_ARG before anything is launched. */
+ * 8192, S > Lcap, fan < 1, B not a multiple of fan, a misaligned pointer or pitch -- return HYENA_ERR_BAD_ARG before anything is launched.
+ *
+ * Block step (hyena_decode_*_block, and *_block_fan for the fan-out layout): T known positions appended per call, 1 <= T <=
+ * HYENA_DECODE_TMAX.  All B rows advance from t0 = *pos (device memory, read by every kernel) to t0 + T:
+ *   x    : (B, T, 3D) `dtype`, the in_proj output of positions t0 ... t0 + T - 1 without bias, element (b, i, c) at (b T + i) ldx + c
+ *   x0   : (B, T, D) fp32 and z : (B, T, D) `dtype`, element (b, i, d) at (b T + i) D + d
+ *   part : hyena_decode_block_partial_floats(B, D, Lcap, T) fp32, [chunk][B][T][D]: part[chunk][b][i][d] = sum over the chunk's s <= t0 + i
+ *          of k[d, t0 + i - s] vg[b, d, s].  A chunk that starts past t0 + i is not read for output i; the fan form writes and reads a
+ *          chunk below S in slot b = g fan only, as hyena_decode_conv_fan does.
+ * hyena_decode_pre_block writes history columns t0 ... t0 + T - 1 and leaves positions t0 + T - 2, t0 + T - 1 in `tail`;
+ * hyena_decode_conv_block streams every history segment ONCE for the T outputs (about the bytes of one single-position step);
+ * hyena_decode_post_block writes z and then sets *pos = t0 + T (a second, one-thread launch on the same stream: the kernel that reads
+ * the position runs on many workgroups).  After one block step, z, x0, the history columns, tail and pos equal what T calls of the
+ * single-position entry points (the fan form: of the _fan entry points) leave, BIT FOR BIT, for the three dtypes: every output keeps
+ * its summation order (csrc/decode_kernels.h).  The history columns up to t0 + T - 1 + 7 must hold finite values (they are read for the
+ * block's earlier outputs against a zero tap).  If t0 < 0 (fan: t0 < S) or t0 + T > Lcap the kernels do nothing and the position stays.
+ * Bad arguments -- T outside [1, HYENA_DECODE_TMAX] and everything the single-position and fan entry points refuse -- return
+ * HYENA_ERR_BAD_ARG before anything is launched.  There is no block form of the per-row (_rows) step. */
 #ifndef HYENA_DECODE_H
 #define HYENA_DECODE_H
 #include <stddef.h>
+#define HYENA_DECODE_TMAX 64
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -71,6 +90,21 @@ int hyena_decode_conv_fan(const float* k, int ldk, const void* vgs, const void* 
                           int Lcap, int S, int lds, int ldr, int dtype, void* stream);
 int hyena_decode_post_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
                           int Lcap, int S, int ldr, int dtype, void* stream);
+
+/* the block step: T positions per call (see the header comment); x (B, T, 3D), x0 and z (B, T, D), part [chunk][B][T][D] */
+size_t hyena_decode_block_partial_floats(int B, int D, int Lcap, int T);
+int hyena_decode_pre_block(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vg, float* x0,
+                           const int* pos, int B, int Bcap, int D, int Lcap, int lda, int T, int dtype, void* stream);
+int hyena_decode_conv_block(const float* k, int ldk, const void* vg, float* part, const int* pos, int B, int D, int Lcap, int lda, int T,
+                            int dtype, void* stream);
+int hyena_decode_post_block(const float* part, const void* vg, const float* fb, const float* x0, void* z, int* pos, int B, int D, int Lcap,
+                            int lda, int T, int dtype, void* stream);
+int hyena_decode_pre_block_fan(const void* x, int ldx, const float* bin, const float* w, const float* b, float* tail, void* vgr, float* x0,
+                               const int* pos, int B, int Bcap, int D, int Lcap, int S, int ldr, int T, int dtype, void* stream);
+int hyena_decode_conv_block_fan(const float* k, int ldk, const void* vgs, const void* vgr, float* part, const int* pos, int B, int fan, int D,
+                                int Lcap, int S, int lds, int ldr, int T, int dtype, void* stream);
+int hyena_decode_post_block_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
+                                int Lcap, int S, int ldr, int T, int dtype, void* stream);
 
 /* Token sampling, the last node of the per-token graph: one wavefront per row of `logits` (B, V) `dtype`, row b at b ldl, 1 <= Vlive <= V <= 64
  * (columns >= Vlive, the padded vocabulary, are never chosen).  Row b stands at column c = col[b] of `seq` (B, ncols) int64, row b at b lds:
