@@ -45,8 +45,9 @@
  *   x    : (B, T, 3D) `dtype`, the in_proj output of positions t0 ... t0 + T - 1 without bias, element (b, i, c) at (b T + i) ldx + c
  *   x0   : (B, T, D) fp32 and z : (B, T, D) `dtype`, element (b, i, d) at (b T + i) D + d
  *   part : hyena_decode_block_partial_floats(B, D, Lcap, T) fp32, [chunk][B][T][D]: part[chunk][b][i][d] = sum over the chunk's s <= t0 + i
- *          of k[d, t0 + i - s] vg[b, d, s].  A chunk that starts past t0 + i is not read for output i; the fan form writes and reads a
- *          chunk below S in slot b = g fan only, as hyena_decode_conv_fan does.
+ *          of k[d, t0 + i - s] vg[b, d, s].  A chunk that starts past t0 + i is not read for output i (a chunk that starts inside the
+ *          block, t0 < chunk * 8192 <= t0 + T - 1, has its slots of the earlier outputs written with 0; chunks past t0 + T - 1 are not
+ *          written at all); the fan form writes and reads a chunk below S in slot b = g fan only, as hyena_decode_conv_fan does.
  * hyena_decode_pre_block writes history columns t0 ... t0 + T - 1 and leaves positions t0 + T - 2, t0 + T - 1 in `tail`;
  * hyena_decode_conv_block streams every history segment ONCE for the T outputs (about the bytes of one single-position step);
  * hyena_decode_post_block writes z and then sets *pos = t0 + T (a second, one-thread launch on the same stream: the kernel that reads
