@@ -11,6 +11,7 @@ HazyResearch/hyena-dna, nothing else.
 * ``hyena_dna_amd.block``    ``dropout_add_layer_norm`` (the block's residual add + LayerNorm, fused)
 * ``hyena_dna_amd.tokenizer``  vectorised DNA character tokenisation (the input side)
 * ``hyena_dna_amd.classifier``  sequence classification on the backbone (``DNAEmbeddingModel``, ``SequenceDecoder``, fused pooled readout)
+* ``hyena_dna_amd.soft_prompt``  soft-prompt tuning of a frozen model (``SoftPromptLM``: evals/soft_prompting_genomics.py), soft tokens inside the first norm
 * ``hyena_dna_amd.csrc``     the HIP kernels and the C ABI (``include/hyena_fftconv.h``, ``hyena_mixer.h``, ``hyena_filter.h``)
 
 There is no CPU or PyTorch fallback for the convolution: without the compiled gfx950 library the ops raise.
@@ -55,5 +56,15 @@ from . import _lib  # noqa: F401,E402
 from ._castcache import invalidate as invalidate_cast_cache  # noqa: F401,E402  (after a parameter write that moves no version counter: _castcache.py)
 
 __all__ = ["fftconv", "hyena", "mixer", "filter", "projection", "block", "tokenizer", "build", "prepare_graph_runtime", "GRAPH_SAFE",
-           "invalidate_cast_cache"]
+           "invalidate_cast_cache", "soft_prompt", "SoftPromptLM", "few_shot_label_positions", "ICLFewShotDataset"]
+
+_LAZY = {"SoftPromptLM": "soft_prompt", "few_shot_label_positions": "soft_prompt", "ICLFewShotDataset": "dataset"}
+
+
+def __getattr__(name):
+    """soft-prompt tuning (soft_prompt.py) and its few-shot dataset, imported on first use: they pull in the whole model"""
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module("." + _LAZY[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 __version__ = "0.1.0"

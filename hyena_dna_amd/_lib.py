@@ -309,6 +309,21 @@ def lib():
         L.hyena_embed_add_norm_bwd.restype = c_int
         L.hyena_embed_add_norm_bwd.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                                c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]
+        L.hyena_soft_embed_add_norm_supported.restype = c_int
+        L.hyena_soft_embed_add_norm_supported.argtypes = [c_int, c_int, c_int]
+        L.hyena_soft_embed_add_norm_fwd.restype = c_int
+        L.hyena_soft_embed_add_norm_fwd.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_long, c_int,
+                                                    c_void_p]
+        L.hyena_soft_embed_add_norm_bwd.restype = c_int
+        L.hyena_soft_embed_add_norm_bwd.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                                    c_float, c_void_p, c_void_p, c_int, c_long, c_long, c_int, c_void_p]
+        L.hyena_row_head_supported.restype = c_int
+        L.hyena_row_head_supported.argtypes = [c_int, c_int, c_int]
+        L.hyena_row_head_fwd.restype = c_int
+        L.hyena_row_head_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]
+        L.hyena_row_head_bwd.restype = c_int
+        L.hyena_row_head_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]
         L.hyena_add_norm_partial_floats.restype = c_size_t
         L.hyena_add_norm_partial_floats.argtypes = [c_long, c_int]
         L.hyena_add_norm_bwd.restype = c_int
@@ -1336,6 +1351,89 @@ def embed_add_norm_bwd(dout, d_res_out, res_out, ids, V, weight, mean, rstd, dro
                                              float(dropout_p), seed.data_ptr() if dropout_p > 0.0 else None, dt.data_ptr(), V,
                                              dw.data_ptr(), db.data_ptr(), part.data_ptr(), rows, D, _backend.stream(dev)))
     return dt, dw, db
+
+
+def soft_embed_add_norm_supported(V, D, out_dtype):
+    try:
+        return bool(lib().hyena_soft_embed_add_norm_supported(int(V), int(D), dtype_code(out_dtype)))
+    except TypeError:
+        return False
+
+
+def _seed_ptr(p, seed, dev):
+    if not p > 0.0:
+        return None
+    assert seed is not None and seed.dtype == torch.int64 and seed.numel() == 1 and seed.device == dev
+    return seed.data_ptr()
+
+
+def soft_embed_add_norm_fwd(ids, table, soft, weight, bias, eps, out_dtype, dropout_p=0.0, seed=None, soft_dropout_p=0.0, soft_seed=None):
+    """ids (B, L) int64, table (V, D) fp32, soft (n, D) fp32 with n >= 1 -> out (B (n + L), D) out_dtype, residual' fp32, mean, rstd (B (n + L),):
+    the first block's norm over [softdrop(soft) | table[ids]] per batch row, neither the embedding nor the concatenation stored
+    (include/hyena_block.h).  Both seeds: one-element int64 tensors on the table's device."""
+    _require_gpu(table, "table")
+    (B, L), (V, D), n = ids.shape, table.shape, soft.shape[0]
+    assert soft.shape == (n, D) and soft.dtype == torch.float32 and table.dtype == torch.float32 and ids.dtype == torch.int64
+    if n < 1 or B < 1 or L < 1:
+        raise ValueError(f"soft_embed_add_norm_fwd needs at least one soft token, one sequence and one position (got n = {n}, B = {B}, L = {L})")
+    dev = table.device
+    rows = B * (n + L)
+    out = torch.empty((rows, D), dtype=out_dtype, device=dev)
+    res_out = torch.empty((rows, D), dtype=torch.float32, device=dev)
+    mean = torch.empty(rows, dtype=torch.float32, device=dev)
+    rstd = torch.empty(rows, dtype=torch.float32, device=dev)
+    with _backend.guard(dev):
+        check(lib().hyena_soft_embed_add_norm_fwd(ids.data_ptr(), table.data_ptr(), V, soft.data_ptr(), float(soft_dropout_p),
+                                                  _seed_ptr(soft_dropout_p, soft_seed, dev), weight.data_ptr(), bias.data_ptr(), float(eps),
+                                                  float(dropout_p), _seed_ptr(dropout_p, seed, dev), out.data_ptr(), dtype_code(out_dtype),
+                                                  res_out.data_ptr(), mean.data_ptr(), rstd.data_ptr(), B, n, L, D, _backend.stream(dev)))
+    return out, res_out, mean, rstd
+
+
+def soft_embed_add_norm_bwd(dout, d_res_out, res_out, weight, mean, rstd, B, n, L, dropout_p=0.0, seed=None, soft_dropout_p=0.0, soft_seed=None):
+    """-> d_soft (n, D) fp32: the gradient of the soft tokens alone (frozen backbone), from the B n soft rows of dout / d_res_out / res_out."""
+    _require_gpu(dout, "dout")
+    rows, D = dout.shape
+    assert rows == B * (n + L) and n >= 1
+    dev = dout.device
+    d_soft = torch.empty((n, D), dtype=torch.float32, device=dev)
+    with _backend.guard(dev):
+        check(lib().hyena_soft_embed_add_norm_bwd(dout.data_ptr(), dtype_code(dout.dtype), None if d_res_out is None else d_res_out.data_ptr(),
+                                                  res_out.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), float(dropout_p),
+                                                  _seed_ptr(dropout_p, seed, dev), float(soft_dropout_p), _seed_ptr(soft_dropout_p, soft_seed, dev),
+                                                  d_soft.data_ptr(), B, n, L, D, _backend.stream(dev)))
+    return d_soft
+
+
+def row_head_supported(V, D, dtype):
+    try:
+        return bool(lib().hyena_row_head_supported(int(V), int(D), dtype_code(dtype)))
+    except TypeError:
+        return False
+
+
+def row_head_fwd(x, weight):
+    """x (rows, D), weight (V, D), one dtype -> logits (rows, V) of that dtype, each accumulated in an order that does not depend on the row count"""
+    _require_gpu(x, "x")
+    (rows, D), V = x.shape, weight.shape[0]
+    assert weight.shape == (V, D) and weight.dtype == x.dtype and weight.device == x.device
+    out = torch.empty((rows, V), dtype=x.dtype, device=x.device)
+    if rows:
+        with _backend.guard(x.device):
+            check(lib().hyena_row_head_fwd(x.data_ptr(), weight.data_ptr(), out.data_ptr(), rows, V, D, dtype_code(x.dtype), _backend.stream(x.device)))
+    return out
+
+
+def row_head_bwd(dy, weight):
+    """dy (rows, V), weight (V, D) -> dx (rows, D) = dy weight"""
+    _require_gpu(dy, "dy")
+    (rows, V), D = dy.shape, weight.shape[1]
+    assert weight.shape == (V, D) and weight.dtype == dy.dtype and weight.device == dy.device
+    dx = torch.empty((rows, D), dtype=dy.dtype, device=dy.device)
+    if rows:
+        with _backend.guard(dy.device):
+            check(lib().hyena_row_head_bwd(dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), rows, V, D, dtype_code(dy.dtype), _backend.stream(dy.device)))
+    return dx
 
 
 def add_norm_bwd(dout, d_res_out, res_out, weight, mean, rstd, dx_dtype, need_dres, dropout_p=0.0, seed=None, offer_colsum=True):

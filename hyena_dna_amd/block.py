@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from . import _lib
 
 __all__ = ["dropout_add_layer_norm", "AddLayerNormFunc", "embedding_dropout_add_layer_norm", "embedding_fusable",
-           "dropout_add_layer_norm_pool", "AddNormPoolFunc"]
+           "dropout_add_layer_norm_pool", "AddNormPoolFunc", "SoftEmbedAddLayerNormFunc", "soft_embedding_dropout_add_layer_norm"]
 
 
 class AddLayerNormFunc(torch.autograd.Function):
@@ -106,6 +106,53 @@ def embedding_dropout_add_layer_norm(ids, table, weight, bias, dropout_p, epsilo
         seed = torch.empty(1, dtype=torch.int64, device=table.device).random_()
         return EmbedAddLayerNormFunc.apply(ids, table, weight, bias, epsilon, out_dtype, float(dropout_p), seed)
     return EmbedAddLayerNormFunc.apply(ids, table, weight, bias, epsilon, out_dtype)
+
+
+class SoftEmbedAddLayerNormFunc(torch.autograd.Function):
+    """(out, residual') of the first block's norm over ``[softdrop(soft) | table[ids]]`` (B, n + L, D) for a FROZEN backbone: neither the
+    embedding nor the concatenation is stored, and the backward returns the gradient of ``soft`` alone, from the B n soft rows
+    (include/hyena_block.h, hyena_soft_embed_add_norm_*).  The caller takes this route only when neither the table nor the norm wants a gradient."""
+
+    @staticmethod
+    def forward(ctx, ids, table, soft, weight, bias, eps, out_dtype, dropout_p=0.0, seed=None, soft_dropout_p=0.0, soft_seed=None):
+        (B, L), n, D = ids.shape, soft.shape[0], table.shape[1]
+        shape = (B, n + L, D)
+        i2 = ids.contiguous()
+        t = table.detach().to(torch.float32).contiguous()
+        s = soft.detach().to(torch.float32).contiguous()
+        w = weight.detach().to(torch.float32).contiguous()
+        b = bias.detach().to(torch.float32).contiguous()
+        out, res_out, mean, rstd = _lib.soft_embed_add_norm_fwd(i2, t, s, w, b, eps, out_dtype, dropout_p=dropout_p, seed=seed,
+                                                                soft_dropout_p=soft_dropout_p, soft_seed=soft_seed)
+        ctx.save_for_backward(res_out, w, mean, rstd)
+        ctx.drop = (float(dropout_p), seed, float(soft_dropout_p), soft_seed)
+        ctx.meta = (B, n, L, D, soft.dtype)
+        return out.view(shape), res_out.view(shape)
+
+    @staticmethod
+    def backward(ctx, dout, dres_out):
+        res_out, w, mean, rstd = ctx.saved_tensors
+        B, n, L, D, s_dtype = ctx.meta
+        d2 = dout.reshape(-1, D).contiguous()
+        h2 = None if dres_out is None else dres_out.reshape(-1, D).to(torch.float32).contiguous()
+        p, seed, sp, sseed = ctx.drop
+        ds = _lib.soft_embed_add_norm_bwd(d2, h2, res_out, w, mean, rstd, B, n, L, dropout_p=p, seed=seed, soft_dropout_p=sp, soft_seed=sseed)
+        return None, None, ds.to(s_dtype), None, None, None, None, None, None, None, None
+
+
+def soft_embedding_dropout_add_layer_norm(ids, table, soft, weight, bias, dropout_p, soft_dropout_p, eps, out_dtype=None):
+    """``dropout_add_layer_norm(torch.cat([F.dropout(soft, soft_dropout_p).expand(B, n, D), F.embedding(ids, table)], 1), None, weight, bias, dropout_p,
+    eps, prenorm=True, residual_in_fp32=True)`` in one pass, differentiable in ``soft`` only (the caller checks ``embedding_fusable``,
+    ``_lib.soft_embed_add_norm_supported`` and that neither ``table`` nor the norm requires a gradient).  Seeds are drawn as
+    ``embedding_dropout_add_layer_norm`` draws its own: the block's first, then the soft tokens'."""
+    if out_dtype is None:
+        out_dtype = torch.float32
+    for name, p in (("dropout", dropout_p), ("soft-token dropout", soft_dropout_p)):
+        if p > 0.0 and not p < 1.0:
+            raise ValueError(f"{name} probability has to be in [0, 1), got {p}")
+    seed = torch.empty(1, dtype=torch.int64, device=table.device).random_() if dropout_p > 0.0 else None
+    soft_seed = torch.empty(1, dtype=torch.int64, device=table.device).random_() if soft_dropout_p > 0.0 else None
+    return SoftEmbedAddLayerNormFunc.apply(ids, table, soft, weight, bias, eps, out_dtype, float(dropout_p), seed, float(soft_dropout_p), soft_seed)
 
 
 def _fused_ok(x0, residual, weight):

@@ -254,6 +254,237 @@ __global__ void __launch_bounds__(BLK_THREADS) add_norm_bwd_kernel(AddNormArgs a
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The FIRST block's norm with a soft prompt in front of the tokens (evals/soft_prompting_genomics.py LitModel.forward:
+// torch.cat([repeat(soft_tokens_drop(soft_tokens), 'n d -> b n d'), embeddings(x)], 1) -> layers[0]):
+//     x0[b, t]  = softdrop(soft)[t]             t < n         (n learnable rows of D fp32, shared by the batch)
+//               = table[ids[b, t - n]]          t >= n
+//     residual' = dropout(x0),   out = LayerNorm(residual')   over the B (n + L) rows, arithmetic of add_norm_fwd_kernel
+// Neither the embedding nor the concatenation is stored.  Two dropouts: the block's, per element of the (B, n + L, D) output from
+// (seed, linear index) as in the plain kernel; the soft tokens', per element of (n, D) from (soft_seed, t D + c) -- the same for
+// every batch row (the reference drops before `repeat`).  The backbone is frozen on this route, so the backward returns d soft
+// alone and reads only the B n soft rows: a wavefront owns a soft position t and adds the rows b = 0 .. B - 1 in order -- no
+// atomics, no partial buffer, one launch, every element of d_soft written.
+// ---------------------------------------------------------------------------------------------------------------
+// no multiply of an earlier statement is fused into the additions of the compound statement this opens (hipcc contracts across statements)
+#ifdef HIPEMU
+#define HY_NO_CONTRACT
+#else
+#define HY_NO_CONTRACT _Pragma("clang fp contract(off)")
+#endif
+enum { SOFT_BATCH_UNROLL = 4 /* batch rows of a soft position whose loads are in flight together (bwd) */ };
+
+struct SoftNormArgs {
+    const long long* ids;   // (B, L) token ids                 fwd
+    const float* table;     // (V, D) fp32                      fwd
+    const float* soft;      // (n, D) fp32                      fwd
+    const void* dout;       // (B (n + L), D) elements of GDT   bwd
+    const float* dres;      // (B (n + L), D) fp32 or null      bwd: gradient w.r.t. residual'
+    const float* saved;     // bwd: residual' as written by the forward
+    const float* weight;    // (D,)
+    const float* bias;      // (D,)  fwd only
+    void* out;              // fwd: (B (n + L), D) elements of ODT
+    float* res_out;         // fwd: residual' fp32
+    float* mean;            // (B (n + L),)  fwd: out, bwd: in
+    float* rstd;
+    float* d_soft;          // bwd: (n, D) fp32
+    int B;
+    long n, L;
+    int D, V;
+    float eps;
+    const unsigned long long* seed;        // the block's dropout (null: none), as AddNormArgs
+    unsigned drop_below;
+    float keep_scale;
+    const unsigned long long* soft_seed;   // the soft tokens' dropout (null: none)
+    unsigned soft_drop_below;
+    float soft_keep_scale;
+};
+
+template <int ODT, int E>
+__global__ void __launch_bounds__(BLK_THREADS) soft_embed_add_norm_fwd_kernel(SoftNormArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = lane * E;
+    float w[E], b[E];
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) { w[e] = a.weight[c0 + e]; b[e] = a.bias[c0 + e]; }
+    const float inv_d = 1.f / (float)a.D;
+    const unsigned long long seed = a.seed != nullptr ? *a.seed : 0ull;
+    const unsigned long long sseed = a.soft_seed != nullptr ? *a.soft_seed : 0ull;
+    const long T = a.n + a.L, rows = (long)a.B * T;
+    // (batch row, position) of a row without a division per row: one for the first row, one for the stride
+    const long row0 = (long)blockIdx.x * BLK_WAVES + wave, stride = (long)gridDim.x * BLK_WAVES;
+    const long stride_b = stride / T, stride_t = stride - stride_b * T;
+    long bi = row0 / T, t = row0 - bi * T;                   // wave-uniform
+    for (long row = row0; row < rows; row += stride, bi += stride_b, t += stride_t) {
+        if (t >= T) { t -= T; ++bi; }
+        const size_t off = (size_t)row * a.D + c0;
+        float r[E];
+        bool bad_id = false;
+        if (t < a.n) {
+            const size_t soff = (size_t)t * a.D + c0;
+            blk_load<DT_F32, E>(a.soft, soff, r);
+            if (a.soft_seed != nullptr) blk_dropout<E>(r, soff, sseed, a.soft_drop_below, a.soft_keep_scale);
+        } else {
+            const long long id = a.ids[bi * a.L + (t - a.n)];
+            bad_id = (unsigned long long)id >= (unsigned long long)a.V;                        // never index the table with it
+            blk_load<DT_F32, E>(a.table, (size_t)(bad_id ? 0 : id) * a.D + c0, r);
+        }
+        if (a.seed != nullptr) blk_dropout<E>(r, off, seed, a.drop_below, a.keep_scale);
+        if (bad_id) {
+            HY_UNROLL
+            for (int e = 0; e < E; ++e) r[e] = __builtin_nanf("");
+        }
+        float s = 0.f;
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) s += r[e];
+        const float mean = wave_sum(s) * inv_d;
+        float v = 0.f;
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) v += (r[e] - mean) * (r[e] - mean);
+        const float rstd = 1.f / sqrtf(wave_sum(v) * inv_d + a.eps);
+        float o[E];
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) o[e] = (r[e] - mean) * rstd * w[e] + b[e];
+        blk_store<ODT, E>(a.out, off, o);
+        blk_store<DT_F32, E>(a.res_out, off, r);
+        if (lane == 0) { a.mean[row] = mean; a.rstd[row] = rstd; }
+    }
+}
+
+template <int GDT, int E>
+__global__ void __launch_bounds__(BLK_THREADS) soft_embed_add_norm_bwd_kernel(SoftNormArgs a) {
+    enum { U = SOFT_BATCH_UNROLL };
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = lane * E;
+    float w[E];
+    HY_UNROLL
+    for (int e = 0; e < E; ++e) w[e] = a.weight[c0 + e];
+    const float inv_d = 1.f / (float)a.D;
+    const unsigned long long seed = a.seed != nullptr ? *a.seed : 0ull;
+    const unsigned long long sseed = a.soft_seed != nullptr ? *a.soft_seed : 0ull;
+    const long T = a.n + a.L;
+    for (long t = (long)blockIdx.x * BLK_WAVES + wave; t < a.n; t += (long)gridDim.x * BLK_WAVES) {
+        float acc[E];
+        HY_UNROLL
+        for (int e = 0; e < E; ++e) acc[e] = 0.f;
+        for (int b0 = 0; b0 < a.B; b0 += U) {
+            // the loads of up to U consecutive batch rows first (independent: all in flight), then their arithmetic in the order of b; a
+            // slot past the batch (wave-uniform) issues no load and no arithmetic
+            float g[U][E], r[U][E], h[U][E], mean[U], rstd[U];
+            size_t off[U];
+            HY_UNROLL
+            for (int u = 0; u < U; ++u) {
+                if (b0 + u >= a.B) break;
+                const long row = (long)(b0 + u) * T + t;
+                off[u] = (size_t)row * a.D + c0;
+                blk_load<GDT, E>(a.dout, off[u], g[u]);
+                blk_load<DT_F32, E>(a.saved, off[u], r[u]);
+                mean[u] = a.mean[row];
+                rstd[u] = a.rstd[row];
+                if (a.dres != nullptr) blk_load<DT_F32, E>(a.dres, off[u], h[u]);
+            }
+            HY_UNROLL
+            for (int u = 0; u < U; ++u) {
+                if (b0 + u >= a.B) break;
+                float s1 = 0.f, s2 = 0.f, xh[E];
+                HY_UNROLL
+                for (int e = 0; e < E; ++e) {
+                    xh[e] = (r[u][e] - mean[u]) * rstd[u];
+                    const float dxh = g[u][e] * w[e];
+                    s1 += dxh;
+                    s2 += dxh * xh[e];
+                }
+                s1 = wave_sum(s1) * inv_d;
+                s2 = wave_sum(s2) * inv_d;
+                float dr[E];
+                HY_UNROLL
+                for (int e = 0; e < E; ++e) dr[e] = rstd[u] * (g[u][e] * w[e] - s1 - xh[e] * s2);
+                if (a.dres != nullptr) {
+                    // (dr is rounded before this add, as in add_norm_bwd_kernel: the sum over b is held to that kernel's dx0 bit for bit)
+                    HY_NO_CONTRACT
+                    HY_UNROLL
+                    for (int e = 0; e < E; ++e) dr[e] += h[u][e];
+                }
+                if (a.seed != nullptr) blk_dropout<E>(dr, off[u], seed, a.drop_below, a.keep_scale);
+                {
+                    HY_NO_CONTRACT                           // (the scaled dx0 of a row is rounded before it joins the sum)
+                    HY_UNROLL
+                    for (int e = 0; e < E; ++e) acc[e] = b0 + u == 0 ? dr[e] : acc[e] + dr[e];
+                }
+            }
+        }
+        const size_t soff = (size_t)t * a.D + c0;
+        if (a.soft_seed != nullptr) blk_dropout<E>(acc, soff, sseed, a.soft_drop_below, a.soft_keep_scale);
+        blk_store<DT_F32, E>(a.d_soft, soff, acc);
+    }
+}
+
+#undef HY_NO_CONTRACT
+
+// ---------------------------------------------------------------------------------------------------------------
+// A row-wise language-model head for the few rows a soft-prompt readout keeps: out[row, v] = sum_c x[row, c] W[v, c], V <= BLK_VMAX token
+// classes.  A library GEMM picks its kernel -- and the order of its additions -- from the row count, so the logits of B n_pos gathered rows
+// are not the bits of the same rows among B L; here a wavefront owns a row (lane l the E channels from l E on, W in registers), every
+// product is accumulated in one fixed order (the lane's E channels, then the 6-step butterfly), and a row's logits do not depend on which
+// other rows the call holds.  x, W and out share one type (fp32, or the 16-bit autocast type: nn.Linear's semantics), sums in fp32.
+// The backward returns dx alone (the head is frozen on this route): dx[row, c] = sum_v dy[row, v] W[v, c], v in order, lane-local.
+// ---------------------------------------------------------------------------------------------------------------
+struct RowHeadArgs {
+    const void* x;          // fwd: (rows, D) elements of DT    bwd: dy (rows, V)
+    const void* w;          // (V, D) elements of DT
+    void* out;              // fwd: (rows, V)                   bwd: dx (rows, D)
+    long rows;
+    int V, D;
+};
+
+template <int DT, int E, bool BWD>
+__global__ void __launch_bounds__(BLK_THREADS) row_head_kernel(RowHeadArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = lane * E;
+    float w[BLK_VMAX][E];
+    HY_UNROLL
+    for (int v = 0; v < BLK_VMAX; ++v) {
+        if (v < a.V) {
+            blk_load<DT, E>(a.w, (size_t)v * a.D + c0, w[v]);
+        } else {
+            HY_UNROLL
+            for (int e = 0; e < E; ++e) w[v][e] = 0.f;
+        }
+    }
+    for (long row = (long)blockIdx.x * BLK_WAVES + wave; row < a.rows; row += (long)gridDim.x * BLK_WAVES) {
+        if (!BWD) {
+            float x[E];
+            blk_load<DT, E>(a.x, (size_t)row * a.D + c0, x);
+            float mine = 0.f;                                // lane v keeps logit v
+            HY_UNROLL
+            for (int v = 0; v < BLK_VMAX; ++v) {
+                if (v < a.V) {                               // wave-uniform
+                    float s = 0.f;
+                    HY_UNROLL
+                    for (int e = 0; e < E; ++e) s += x[e] * w[v][e];
+                    s = wave_sum(s);
+                    mine = lane == v ? s : mine;
+                }
+            }
+            if (lane < a.V) reinterpret_cast<elem_t*>(a.out)[(size_t)row * a.V + lane] = Elem<DT>::cvt(mine);
+        } else {
+            float dx[E];
+            HY_UNROLL
+            for (int e = 0; e < E; ++e) dx[e] = 0.f;
+            HY_UNROLL
+            for (int v = 0; v < BLK_VMAX; ++v) {
+                if (v < a.V) {
+                    const float g = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.x)[(size_t)row * a.V + v]);
+                    HY_UNROLL
+                    for (int e = 0; e < E; ++e) dx[e] += g * w[v][e];
+                }
+            }
+            blk_store<DT, E>(a.out, (size_t)row * a.D + c0, dx);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // The pooled readout of a sequence classifier (src/tasks/decoders.py SequenceDecoder, mode pool / sum, on top of the backbone's
 // final norm, long_conv_lm.py:381-396):
 //     pooled[b, :] = scale_b * sum_{t < n_b} LayerNorm(dropout(x0[b, t]) + residual[b, t])        scale_b = 1 / n_b (mean) or 1 (sum)

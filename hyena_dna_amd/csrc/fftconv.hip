@@ -988,6 +988,127 @@ int hyena_embed_add_norm_bwd(const void* dout, int dout_dtype, const float* d_re
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
+extern "C++" {
+namespace {
+// the soft-prompt forms of the first block's norm (block_kernels.h, SoftNormArgs)
+bool soft_dropout_params(float p, const unsigned long long* seed, const unsigned long long*& seed_out, unsigned& below, float& scale) {
+    AddNormArgs t;
+    if (!blk_set_dropout(t, p, seed)) return false;
+    seed_out = t.seed; below = t.drop_below; scale = t.keep_scale;
+    return true;
+}
+template <int ODT>
+int soft_launch_fwd(const SoftNormArgs& a, void* stream) {
+    const int grid = blk_grid((long)a.B * (a.n + a.L));
+    switch (a.D / 64) {
+        case 1: HY_LAUNCH((soft_embed_add_norm_fwd_kernel<ODT, 1>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 2: HY_LAUNCH((soft_embed_add_norm_fwd_kernel<ODT, 2>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 4: HY_LAUNCH((soft_embed_add_norm_fwd_kernel<ODT, 4>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        default: return HYENA_ERR_BAD_ARG;
+    }
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+template <int GDT>
+int soft_launch_bwd(const SoftNormArgs& a, void* stream) {
+    const int grid = blk_grid(a.n);
+    switch (a.D / 64) {
+        case 1: HY_LAUNCH((soft_embed_add_norm_bwd_kernel<GDT, 1>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 2: HY_LAUNCH((soft_embed_add_norm_bwd_kernel<GDT, 2>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 4: HY_LAUNCH((soft_embed_add_norm_bwd_kernel<GDT, 4>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        default: return HYENA_ERR_BAD_ARG;
+    }
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+SoftNormArgs soft_args(int B, long n, long L, int D, int V) {
+    SoftNormArgs a;
+    a.ids = nullptr; a.table = nullptr; a.soft = nullptr; a.dout = nullptr; a.dres = nullptr; a.saved = nullptr; a.weight = nullptr;
+    a.bias = nullptr; a.out = nullptr; a.res_out = nullptr; a.mean = nullptr; a.rstd = nullptr; a.d_soft = nullptr;
+    a.B = B; a.n = n; a.L = L; a.D = D; a.V = V; a.eps = 0.f;
+    return a;
+}
+}  // namespace
+}  // extern "C++": templates
+
+int hyena_soft_embed_add_norm_supported(int V, int D, int out_dtype) { return hyena_embed_add_norm_supported(V, D, out_dtype); }
+
+int hyena_soft_embed_add_norm_fwd(const long long* ids, const float* table, int V, const float* soft, float soft_dropout_p,
+                                  const unsigned long long* soft_seed, const float* weight, const float* bias, float eps, float dropout_p,
+                                  const unsigned long long* seed, void* out, int out_dtype, float* residual_out, float* mean, float* rstd,
+                                  int B, long n, long L, int D, void* stream) {
+    if (ids == nullptr || table == nullptr || soft == nullptr || weight == nullptr || bias == nullptr || out == nullptr ||
+        residual_out == nullptr || mean == nullptr || rstd == nullptr || B < 1 || n < 1 || L < 1 ||
+        !hyena_soft_embed_add_norm_supported(V, D, out_dtype))
+        return HYENA_ERR_BAD_ARG;
+    SoftNormArgs a = soft_args(B, n, L, D, V);
+    a.ids = ids; a.table = table; a.soft = soft; a.weight = weight; a.bias = bias; a.out = out; a.res_out = residual_out;
+    a.mean = mean; a.rstd = rstd; a.eps = eps;
+    if (!soft_dropout_params(dropout_p, seed, a.seed, a.drop_below, a.keep_scale) ||
+        !soft_dropout_params(soft_dropout_p, soft_seed, a.soft_seed, a.soft_drop_below, a.soft_keep_scale))
+        return HYENA_ERR_BAD_ARG;
+    switch (out_dtype) {
+        case HYENA_F32: return soft_launch_fwd<DT_F32>(a, stream);
+        case HYENA_BF16: return soft_launch_fwd<DT_BF16>(a, stream);
+        default: return soft_launch_fwd<DT_F16>(a, stream);
+    }
+}
+
+int hyena_soft_embed_add_norm_bwd(const void* dout, int dout_dtype, const float* d_residual_out, const float* residual_out,
+                                  const float* weight, const float* mean, const float* rstd, float dropout_p,
+                                  const unsigned long long* seed, float soft_dropout_p, const unsigned long long* soft_seed,
+                                  float* d_soft, int B, long n, long L, int D, void* stream) {
+    if (dout == nullptr || residual_out == nullptr || weight == nullptr || mean == nullptr || rstd == nullptr || d_soft == nullptr ||
+        B < 1 || n < 1 || L < 1 || !hyena_soft_embed_add_norm_supported(1, D, dout_dtype))
+        return HYENA_ERR_BAD_ARG;
+    SoftNormArgs a = soft_args(B, n, L, D, 0);
+    a.dout = dout; a.dres = d_residual_out; a.saved = residual_out; a.weight = weight; a.mean = const_cast<float*>(mean);
+    a.rstd = const_cast<float*>(rstd); a.d_soft = d_soft;
+    if (!soft_dropout_params(dropout_p, seed, a.seed, a.drop_below, a.keep_scale) ||
+        !soft_dropout_params(soft_dropout_p, soft_seed, a.soft_seed, a.soft_drop_below, a.soft_keep_scale))
+        return HYENA_ERR_BAD_ARG;
+    switch (dout_dtype) {
+        case HYENA_F32: return soft_launch_bwd<DT_F32>(a, stream);
+        case HYENA_BF16: return soft_launch_bwd<DT_BF16>(a, stream);
+        default: return soft_launch_bwd<DT_F16>(a, stream);
+    }
+}
+
+extern "C++" {
+namespace {
+template <int DT, bool BWD>
+int row_head_launch(const RowHeadArgs& a, void* stream) {
+    const int grid = blk_grid(a.rows);
+    switch (a.D / 64) {
+        case 1: HY_LAUNCH((row_head_kernel<DT, 1, BWD>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 2: HY_LAUNCH((row_head_kernel<DT, 2, BWD>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        case 4: HY_LAUNCH((row_head_kernel<DT, 4, BWD>), dim3(grid), dim3(BLK_THREADS), 0, stream, a); break;
+        default: return HYENA_ERR_BAD_ARG;
+    }
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+template <bool BWD>
+int row_head_call(const void* x, const void* w, void* out, long rows, int V, int D, int dtype, void* stream) {
+    if (x == nullptr || w == nullptr || out == nullptr || rows < 1 || !hyena_embed_add_norm_supported(V, D, dtype)) return HYENA_ERR_BAD_ARG;
+    RowHeadArgs a;
+    a.x = x; a.w = w; a.out = out; a.rows = rows; a.V = V; a.D = D;
+    switch (dtype) {
+        case HYENA_F32: return row_head_launch<DT_F32, BWD>(a, stream);
+        case HYENA_BF16: return row_head_launch<DT_BF16, BWD>(a, stream);
+        default: return row_head_launch<DT_F16, BWD>(a, stream);
+    }
+}
+}  // namespace
+}  // extern "C++": templates
+
+int hyena_row_head_supported(int V, int D, int dtype) { return hyena_embed_add_norm_supported(V, D, dtype); }
+
+int hyena_row_head_fwd(const void* x, const void* weight, void* out, long rows, int V, int D, int dtype, void* stream) {
+    return row_head_call<false>(x, weight, out, rows, V, D, dtype, stream);
+}
+
+int hyena_row_head_bwd(const void* dy, const void* weight, void* dx, long rows, int V, int D, int dtype, void* stream) {
+    return row_head_call<true>(dy, weight, dx, rows, V, D, dtype, stream);
+}
+
 size_t hyena_add_norm_partial_floats(long rows, int D) {
     if (rows < 1 || D < 1) return 0;
     return (size_t)blk_grid(rows) * 3 * D;          // (dweight | dbias | column sums of dx0: the third plane is used by the _colsum entry point only)

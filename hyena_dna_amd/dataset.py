@@ -26,7 +26,7 @@ import torch
 
 from .tokenizer import DNACharTokenizerLUT
 
-__all__ = ["FastaIndex", "FastaInterval", "HG38Dataset", "reverse_complement"]
+__all__ = ["FastaIndex", "FastaInterval", "HG38Dataset", "ICLFewShotDataset", "reverse_complement"]
 
 _RC = np.arange(256, dtype=np.uint8)
 for _a, _b in zip(b"ACGTacgt", b"TGCAtgca"):
@@ -231,3 +231,64 @@ class HG38Dataset(torch.utils.data.Dataset):
         chr_name, start, end = self.rows[idx]
         seq = self.fasta.fetch_bytes(chr_name, start, end, max_length=self.max_length)
         return self.lut.sample(seq, self.max_length, add_eos=self.add_eos, replace_N_token=self.replace_N_token)
+
+
+class ICLFewShotDataset(torch.utils.data.Dataset):
+    """Few-shot prompts over IN-MEMORY sequences, in the sample layout of the reference's in-context-learning dataset
+    (src/dataloaders/datasets/icl_genomics_dataset.py): nothing is downloaded, no ``genomic_benchmarks``.
+
+        shots = 0:  (seq + eos,                                                         label)
+        shots = k:  (k demonstrations per class, shuffled, each seq + eos + label + eos,  then seq + eos,  label)
+
+    ``sequences``: str / bytes, cut to ``max_length`` characters, tokenised without special tokens or padding; ``labels``: ints;
+    ``label_to_token``: label -> a character of the tokenizer (a longer string is looked up in its vocabulary, [UNK] if absent; default
+    ``{0: "A", 1: "N"}`` as there).  The demonstrations of a class are drawn without replacement among the other samples of that class: one
+    ``np.random.choice`` per class in ascending label order, then one ``np.random.shuffle`` over all of them.  With sequences of exactly
+    ``max_length`` characters and ``add_eos`` the label tokens of ``cat([x, y])`` sit at
+    ``soft_prompt.few_shot_label_positions(max_length, len(x) + 1)``."""
+
+    def __init__(self, sequences, labels, shots, max_length, tokenizer=None, label_to_token=None, add_eos=True, rc_aug=False):
+        if len(sequences) != len(labels):
+            raise ValueError(f"{len(sequences)} sequences but {len(labels)} labels")
+        self.shots, self.max_length, self.add_eos, self.rc_aug = int(shots), int(max_length), bool(add_eos), bool(rc_aug)
+        self.tokenizer = tok = tokenizer if tokenizer is not None else DNACharTokenizerLUT()
+        self.label_to_token = {0: "A", 1: "N"} if label_to_token is None else dict(label_to_token)
+        self._text = [bytes(s) if isinstance(s, (bytes, bytearray)) else s.encode("ascii", "replace") for s in sequences]
+        self._y = np.asarray([int(y) for y in labels], dtype=np.int64)
+        classes = np.unique(self._y)                                 # ascending
+        self.d_output = len(classes)
+        self._members = [np.flatnonzero(self._y == c) for c in classes]
+        for c, members in zip(classes, self._members):
+            if self.shots > 0 and len(members) < self.shots + 1:
+                raise ValueError(f"label {int(c)} has fewer than shots + 1 = {self.shots + 1} samples")
+        self._label_token = {}
+        for c in classes:
+            name = self.label_to_token[int(c)]
+            self._label_token[int(c)] = (int(tok._lut[ord(name)]) if len(name) == 1 and ord(name) < 256
+                                         else int(tok.vocab.get(name, tok.unk_token_id)))
+        self._eos = int(tok.sep_token_id)
+
+    def __len__(self):
+        return len(self._text)
+
+    def _encode(self, i):
+        """token ids of sequence i (int64 array), reverse-complemented on a coin flip with ``rc_aug``, with the eos if ``add_eos``"""
+        raw = self._text[i][:self.max_length]
+        if self.rc_aug and coin_flip():
+            raw = reverse_complement(raw)
+        ids = self.tokenizer._lut[np.frombuffer(raw, dtype=np.uint8)].astype(np.int64)
+        return np.append(ids, self._eos) if self.add_eos else ids
+
+    def __getitem__(self, idx):
+        demos = []
+        if self.shots > 0:
+            drawn = [np.random.choice(members[members != idx], size=self.shots, replace=False) for members in self._members]
+            demos = np.stack(drawn, axis=1).reshape(-1).tolist()        # classes interleaved, then shuffled as one list
+            np.random.shuffle(demos)
+        tail = (self._eos,) if self.add_eos else ()
+        parts = []
+        for i in demos:
+            parts += [self._encode(i), (self._label_token[int(self._y[i])],) + tail]
+        parts.append(self._encode(idx))
+        x = np.concatenate([np.asarray(p, dtype=np.int64) for p in parts])
+        return torch.from_numpy(x), torch.tensor([self._label_token[int(self._y[idx])]], dtype=torch.int64)

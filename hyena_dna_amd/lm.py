@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .block import dropout_add_layer_norm, embedding_dropout_add_layer_norm, embedding_fusable
+from .block import dropout_add_layer_norm, embedding_dropout_add_layer_norm, embedding_fusable, soft_embedding_dropout_add_layer_norm
 from .projection import hyena_linear
 
 __all__ = ["Mlp", "Block", "GPT2Embeddings", "MHA", "GenerationMixin", "HyenaDNALM", "GraphedDecodeStep", "sync_shared_params", "all_gather_raw"]
@@ -704,20 +704,72 @@ class HyenaDNALM(nn.Module, GenerationMixin):
     def tie_weights(self):
         self.lm_head.weight = self.backbone.embeddings.word_embeddings.weight
 
-    def hidden(self, input_ids, position_ids=None, inference_params=None):
-        return self._final_norm(*self.trunk(input_ids, position_ids, inference_params=inference_params))
+    def hidden(self, input_ids, position_ids=None, inference_params=None, soft_tokens=None, soft_dropout_p=0.0):
+        return self._final_norm(*self.trunk(input_ids, position_ids, inference_params=inference_params, soft_tokens=soft_tokens,
+                                            soft_dropout_p=soft_dropout_p))
 
-    def trunk(self, input_ids, position_ids=None, inference_params=None):
+    def _embedding_fusion_ok(self, input_ids):
+        """the first block's norm can gather the token embedding itself (block.embedding_fusable + this model's configuration)"""
+        bb = self.backbone
+        emb, blk0 = bb.embeddings, bb.layers[0]
+        return (self.fused_dropout_add_ln and self.residual_in_fp32 and isinstance(blk0, Block) and blk0.prenorm and blk0.fused_dropout_add_ln
+                and blk0.residual_in_fp32 and emb.project_in is None and emb.max_position_embeddings <= 0
+                and embedding_fusable(input_ids, emb.word_embeddings, blk0.norm1.weight))
+
+    def _trunk_soft(self, input_ids, position_ids, soft_tokens, soft_dropout_p, fused=True):
+        """``trunk`` over ``[dropout(soft_tokens) | embeddings(input_ids)]`` (B, n + L, D): the reference's soft prompting
+        (evals/soft_prompting_genomics.py LitModel.forward).  Token positions count from 0 and the soft tokens get no position embedding, as
+        there.  Fused into the first block's norm (block.soft_embedding_dropout_add_layer_norm) when the embedding fusion applies, the kernels
+        cover the shape and neither the table nor norm1 wants a gradient (the pass returns the soft tokens' gradient only); otherwise the
+        reference's own statement, ``torch.cat``, in front of the blocks as they are."""
+        from . import _lib
+        bb = self.backbone
+        emb, blk0 = bb.embeddings, bb.layers[0]
+        if soft_tokens.dim() != 2 or soft_tokens.shape[1] != self.d_model or soft_tokens.shape[0] < 1:
+            raise ValueError(f"soft_tokens has to be (n >= 1, {self.d_model}), got {tuple(soft_tokens.shape)}")
+        B, L = input_ids.shape
+        n = soft_tokens.shape[0]
+        for mixer in self._mixers():
+            l_max = getattr(mixer, "l_max", None)
+            if l_max is not None and n + L > l_max:
+                raise ValueError(f"{n} soft tokens + {L} positions = {n + L} exceed a mixer's l_max = {l_max}")
+        sp = float(soft_dropout_p) if self.training else 0.0
+        if (fused and self._embedding_fusion_ok(input_ids) and soft_tokens.dtype == torch.float32 and soft_tokens.device == input_ids.device
+                and _lib.soft_embed_add_norm_supported(emb.word_embeddings.weight.shape[0], self.d_model, torch.float32)
+                and not (torch.is_grad_enabled() and (emb.word_embeddings.weight.requires_grad or blk0.norm1.weight.requires_grad
+                                                      or blk0.norm1.bias.requires_grad))):
+            dev_type = input_ids.device.type
+            odt = torch.get_autocast_dtype(dev_type) if torch.is_autocast_enabled(dev_type) else torch.float32
+            if odt not in (torch.bfloat16, torch.float16):
+                odt = torch.float32
+            hidden_states, residual = soft_embedding_dropout_add_layer_norm(
+                input_ids, emb.word_embeddings.weight, soft_tokens, blk0.norm1.weight, blk0.norm1.bias, blk0.dropout1.p if self.training else 0.0,
+                sp, blk0.norm1.eps, out_dtype=odt)
+            hidden_states, residual = blk0(hidden_states, residual, normed=True)
+            rest = list(bb.layers)[1:]
+        else:
+            tokens = emb(input_ids, position_ids=position_ids)
+            soft = F.dropout(soft_tokens, sp, training=True) if sp > 0.0 else soft_tokens
+            hidden_states, residual = torch.cat([soft.to(tokens.dtype).unsqueeze(0).expand(B, n, self.d_model), tokens], 1), None
+            rest = bb.layers
+        for blk in rest:
+            hidden_states, residual = blk(hidden_states, residual)
+        return hidden_states, residual
+
+    def trunk(self, input_ids, position_ids=None, inference_params=None, soft_tokens=None, soft_dropout_p=0.0, soft_fused=True):
         """(hidden_states, residual) as the last block leaves them, in front of drop_f / ln_f (long_conv_lm.py:367-380): what a readout that
-        carries the final norm inside its own pass starts from (classifier.HyenaDNAClassifier)"""
+        carries the final norm inside its own pass starts from (classifier.HyenaDNAClassifier).  ``soft_tokens`` (n, D): learnable embeddings in
+        front of the tokens -- the outputs are (B, n + L, ...) (``_trunk_soft``); None: the token-only path."""
+        if soft_tokens is not None:
+            if inference_params is not None:
+                raise NotImplementedError("cached decoding with a soft prefix is not supported")
+            return self._trunk_soft(input_ids, position_ids, soft_tokens, soft_dropout_p, fused=soft_fused)
         bb = self.backbone
         emb, blk0 = bb.embeddings, bb.layers[0]
         # inference_params reach every mixer through the block's mixer_kwargs (long_conv_lm.py:375-378); a non-empty mixer_kwargs also keeps the
         # block off forward_add_norm
         mk = (lambda: None) if inference_params is None else (lambda: {"inference_params": inference_params})
-        if (self.fused_dropout_add_ln and self.residual_in_fp32 and isinstance(blk0, Block) and blk0.prenorm and blk0.fused_dropout_add_ln
-                and blk0.residual_in_fp32 and emb.project_in is None and emb.max_position_embeddings <= 0
-                and embedding_fusable(input_ids, emb.word_embeddings, blk0.norm1.weight)):
+        if self._embedding_fusion_ok(input_ids):
             # the token embedding gathered inside the first block's dropout -> add -> LayerNorm pass (block.py): neither the (B, L, D) fp32
             # embedding nor its gradient exists; the normed output leaves in the autocast type the mixer would round it to anyway
             dev_type = input_ids.device.type
@@ -757,7 +809,10 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         layer's l_max admits the padded length (hg38 configurations: l_max = max_length + 2) and the fused kernels are in use -- and only for a
         CAUSAL stack: a bidirectional filter (HyenaFilter(bidirectional=True)) centres the input in a 2 L window, so the padded length moves every
         output; a mixer that is not a HyenaOperator is not known to be causal.  Such models run at the length they are given."""
-        B, L = input_ids.shape
+        return self._aligned_total(input_ids.shape[0], input_ids.shape[1], input_ids.is_cuda)
+
+    def _aligned_total(self, B, L, on_device):
+        """``_aligned_length``'s rule for B sequences of L positions in all (with a soft prefix: n + L)"""
         # ONE odd-length sequence: its rows are aligned (pitched), what is left are the library weight-gradient products over an odd number of
         # positions (2^20 - 1: dW1 712 vs 612 us, dW_in 611 vs 571, dW_out 303 vs 260 per layer: profiles/r6_wgrad_plan.txt).  Padded where that
         # turns them into the aligned one-level plan -- the padded length a multiple of 4096 (2^20 - 1, 32767: model step 157.5 -> 156.3 ms at
@@ -767,7 +822,7 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         if B <= 1 and (L < _PAD_SINGLE_MIN or (L + (-L) % _SEQ_ALIGN) % _PAD_SINGLE_ROWS != 0):
             return L
         from . import _lib
-        if not (input_ids.is_cuda or _lib._backend.name != "hip"):
+        if not (on_device or _lib._backend.name != "hip"):
             return L
         Lp = L + (-L) % _SEQ_ALIGN
         emb = self.backbone.embeddings
@@ -780,6 +835,35 @@ class HyenaDNALM(nn.Module, GenerationMixin):
             if mixer.l_max < Lp:
                 return L
         return Lp
+
+    def hidden_at(self, input_ids, positions=None, soft_tokens=None, soft_dropout_p=0.0, soft_fused=True):
+        """the final norm's output (B, n_pos, D) at ``positions``, an (n_pos,) int64 index into the L INPUT positions shared by the batch (None: all
+        of them); soft positions are never returned.  (hidden, residual) are gathered in front of drop_f / ln_f: the norm and whatever head
+        follows are per-position, so they run on B n_pos rows instead of B (n + L) and give the rows of the full computation.  The end-padding
+        rule of ``_aligned_length`` applies to the total n + L: pad ids are appended, their positions dropped here."""
+        if positions is None:
+            # all positions: the norm runs over the n + L (+ pad) rows as they lie and its output is sliced -- a view; cutting the soft rows
+            # out in front of it would copy B L D elements of hidden and of the residual, and scatter as many in the backward
+            normed, n = self._hidden_all(input_ids, soft_tokens, soft_dropout_p, soft_fused)
+            return normed[:, n:n + input_ids.shape[1]]
+        if positions.dim() != 1 or positions.dtype != torch.int64:
+            raise ValueError("positions has to be an (n_pos,) int64 index")
+        hidden_states, residual, n = self._trunk_padded(input_ids, soft_tokens, soft_dropout_p, soft_fused)
+        idx = positions.to(hidden_states.device) + n
+        return self._final_norm(hidden_states.index_select(1, idx), residual.index_select(1, idx))
+
+    def _trunk_padded(self, input_ids, soft_tokens, soft_dropout_p, soft_fused):
+        """(hidden_states, residual, n) of ``trunk`` over the n soft + L input positions, end-padded by ``_aligned_total``'s rule"""
+        B, L = input_ids.shape
+        n = 0 if soft_tokens is None else soft_tokens.shape[0]
+        Tp = self._aligned_total(B, n + L, input_ids.is_cuda)
+        ids = F.pad(input_ids, (0, Tp - n - L), value=0) if Tp != n + L else input_ids
+        return self.trunk(ids, soft_tokens=soft_tokens, soft_dropout_p=soft_dropout_p, soft_fused=soft_fused) + (n,)
+
+    def _hidden_all(self, input_ids, soft_tokens=None, soft_dropout_p=0.0, soft_fused=True):
+        """(final norm's output over ALL rows (B, n + L + pad, D), n): the input positions are [:, n:n + L]"""
+        hidden_states, residual, n = self._trunk_padded(input_ids, soft_tokens, soft_dropout_p, soft_fused)
+        return self._final_norm(hidden_states, residual), n
 
     def _mixers(self):
         return [getattr(blk.mixer, "layer", blk.mixer) for blk in self.backbone.layers]      # (a CheckpointedModule is unwrapped)
