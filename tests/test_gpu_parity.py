@@ -54,7 +54,9 @@ def test_native_library_is_the_one_loaded(gpu_lib):
     (2, 3, 1, None), (2, 3, 8, None), (3, 5, 1023, None), (8, 128, 1024, None), (2, 4, 1025, 3), (2, 3, 2048, None),
     (1, 3, 5000, None), (2, 2, 8191, None), (1, 4, 16384, 1), (2, 8, 32768, None), (1, 2, 65536, None),
     (1, 3, 160000, 2), (1, 2, 450560, None), (1, 2, 1048576, None), (1, 1, 1048575, None),
-    # column sizes that are not powers of two (M1 = 3, 5, 7, 12, 28, 96, 224, 384, 640, 768)
+    # lengths of the form 1024 M1 - 3 with M1 no power of two.  Only M1 = 96, 224, 384, 640, 768 still reach the two-level column kernels: the
+    # first five (M1 = 3, 5, 7, 12, 28 before the workspace-free plan took over L <= 32768) run on that plan today, as ragged rows of its
+    # transform sizes 4096 ... 32768.  The two-level kernels at M1 <= 32: tests/test_gpu_fftconv_local.py, under HYENA_FFTCONV_ONCHIP=0.
     (2, 3, 3069, None), (2, 2, 5117, None), (2, 2, 7165, 1), (1, 3, 12285, None), (1, 2, 28669, None), (1, 2, 98301, None),
     (1, 2, 229373, None), (1, 1, 393213, None), (1, 1, 655357, None), (1, 1, 786429, None),
 ])
