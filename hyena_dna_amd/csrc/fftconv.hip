@@ -771,7 +771,7 @@ int hyena_filter_bwd(const hyena_filter_params* p, const float* dk, const float*
 }
 
 int hyena_filter_fwd_ld(const hyena_filter_params* p, float* k, int ldk, float* saved, void* stream) {
-    if (!flt_params_ok(p) || k == nullptr || ldk < p->L) return HYENA_ERR_BAD_ARG;
+    if (!flt_params_ok(p) || k == nullptr || ldk < p->L || !flt_pitch_ok(p->D, ldk)) return HYENA_ERR_BAD_ARG;
     FilterArgs a;
     a.z = p->z; a.t = p->t; a.w0 = p->w0; a.b0 = p->b0; a.w1 = p->w1; a.b1 = p->b1; a.w2 = p->w2; a.b2 = p->b2; a.w3 = p->w3;
     a.freq = p->freq; a.deltas = p->deltas; a.k = k; a.acts = saved; a.shift = p->shift; a.modulate = p->modulate;
@@ -786,7 +786,8 @@ int hyena_filter_fwd_ld(const hyena_filter_params* p, float* k, int ldk, float* 
 
 int hyena_filter_bwd_ld(const hyena_filter_params* p, const float* dk, int ldk, const float* saved, const hyena_filter_grads* g,
                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!flt_params_ok(p) || dk == nullptr || saved == nullptr || g == nullptr || workspace == nullptr || ldk < p->L) return HYENA_ERR_BAD_ARG;
+    if (!flt_params_ok(p) || dk == nullptr || saved == nullptr || g == nullptr || workspace == nullptr || ldk < p->L || !flt_pitch_ok(p->D, ldk))
+        return HYENA_ERR_BAD_ARG;
     if (!g->dw0 || !g->db0 || !g->dw1 || !g->db1 || !g->dw2 || !g->db2 || !g->dw3 || !g->dfreq) return HYENA_ERR_BAD_ARG;
     if (workspace_bytes < hyena_filter_workspace_bytes(p->L, p->D)) return HYENA_ERR_WORKSPACE;
     const int L = p->L, P = hyena_filter_row_pitch(L);

@@ -143,7 +143,7 @@ int hyena_filter16_bwd(const hyena_filter_params* p, int dtype, const float* dk,
 }
 
 int hyena_filter16_fwd_ld(const hyena_filter_params* p, int dtype, float* k, int ldk, void* saved, void* stream) {
-    if (!f16_params_ok(p, dtype) || k == nullptr || ldk < p->L) return HYENA_ERR_BAD_ARG;
+    if (!f16_params_ok(p, dtype) || k == nullptr || ldk < p->L || !flt_pitch_ok(p->D, ldk)) return HYENA_ERR_BAD_ARG;
     FilterArgs a;
     a.z = p->z; a.t = p->t; a.w0 = p->w0; a.b0 = p->b0; a.w1 = p->w1; a.b1 = p->b1; a.w2 = p->w2; a.b2 = p->b2; a.w3 = p->w3;
     a.freq = p->freq; a.deltas = p->deltas; a.k = k; a.acts = static_cast<float*>(saved); a.shift = p->shift; a.modulate = p->modulate;
@@ -155,7 +155,8 @@ int hyena_filter16_fwd_ld(const hyena_filter_params* p, int dtype, float* k, int
 
 int hyena_filter16_bwd_ld(const hyena_filter_params* p, int dtype, const float* dk, int ldk, const void* saved, const hyena_filter_grads* g,
                           void* workspace, size_t workspace_bytes, void* stream) {
-    if (!f16_params_ok(p, dtype) || dk == nullptr || saved == nullptr || g == nullptr || workspace == nullptr || ldk < p->L) return HYENA_ERR_BAD_ARG;
+    if (!f16_params_ok(p, dtype) || dk == nullptr || saved == nullptr || g == nullptr || workspace == nullptr || ldk < p->L || !flt_pitch_ok(p->D, ldk))
+        return HYENA_ERR_BAD_ARG;
     if (!g->dw0 || !g->db0 || !g->dw1 || !g->db1 || !g->dw2 || !g->db2 || !g->dw3 || !g->dfreq) return HYENA_ERR_BAD_ARG;
     if (workspace_bytes < hyena_filter_workspace_bytes(p->L, p->D)) return HYENA_ERR_WORKSPACE;
     if (dtype == HYENA_BF16) bwd_all<DT_BF16>(p, dk, ldk, saved, g, workspace, stream);

@@ -30,7 +30,8 @@
 // reference's autograd keeps (z W^T, f*a, sin(...) per layer, some twice under autocast).
 //
 // Precision: fp32 throughout (v_mfma_f32_32x32x2_f32 is exact fp32 FMA arithmetic) -- the graph the reference computes without
-// autocast; it agrees with the fp32 reference to ~1e-6 (tests/test_filter_*.py state the tolerances).  Under torch.autocast the
+// autocast; it agrees with the fp32 reference to ~1e-6 in norm (tests/test_filter_emu.py, tests/test_gpu_filter.py) and is held element by
+// element to fp64 references with bounds derived from fp32 arithmetic (tests/filter_local.py, profiles/filter_local.md).  Under torch.autocast the
 // reference runs the four GEMMs in the 16-bit type: that graph is filter16_kernels.h's (this header's first-layer backward kernel
 // serves it too, with its operands rounded on load: FilterBwdArgs::rdt).
 #pragma once
@@ -624,6 +625,10 @@ __global__ void __launch_bounds__(256) filter_compact_kernel(const float* src, f
 }
 
 #endif  // FLT_DECLARE_ONLY
+
+// host side: the kernels address row d of k / dk by the 32-bit byte offset vpos + d * ldk * 4 and hand lanes past the end FLT_OOB + d * ldk * 4;
+// neither sum wraps, and the descriptor's 32-bit size (unsigned)(D * ldk * 4) is the buffer's, only while D * ldk * 4 <= 2^31
+inline bool flt_pitch_ok(int D, int ldk) { return (unsigned long long)D * (unsigned long long)ldk * 4ull <= 0x80000000ull; }
 
 // host side: collect up to four reductions, then one launch
 struct RedBatch {

@@ -94,7 +94,9 @@ int hyena_filter16_bwd(const hyena_filter_params* p, int dtype, const float* dk,
  * rows of a packed (D, L) fp32 tensor are 4-byte but not 16-byte aligned.  `ldk` = floats between the starts of consecutive rows of k / dk
  * (ldk >= L; elements [L, ldk) of a row are never read or written) -- the same pitch hyena_fftconv_fwd_ld / _bwd_ld take for them.  The entry
  * points above are these with ldk = L.  The library-owned buffers (`saved`, the backward's workspace) are pitched internally to
- * hyena_filter_row_pitch(L) = L rounded up to 64 words: their sizes are what hyena_filter*_saved_bytes / _workspace_bytes return. */
+ * hyena_filter_row_pitch(L) = L rounded up to 64 words: their sizes are what hyena_filter*_saved_bytes / _workspace_bytes return.
+ * The kernels address k / dk by 32-bit byte offsets: D * ldk * 4 must not exceed 2^31 (ldk <= 2^21 at D = 256; every packed or pitched row
+ * up to HYENA_MAX_L is far below).  A larger pitch returns HYENA_ERR_BAD_ARG before anything is launched. */
 int hyena_filter_row_pitch(int L);
 int hyena_filter_fwd_ld(const hyena_filter_params* p, float* k, int ldk, float* saved, void* stream);
 int hyena_filter_bwd_ld(const hyena_filter_params* p, const float* dk, int ldk, const float* saved, const hyena_filter_grads* g,
