@@ -220,7 +220,7 @@ class SmallVocabEmbeddingFunc(torch.autograd.Function):
     def backward(ctx, dh):
         from .projection import split_k_weight_grad
         (ids,) = ctx.saved_tensors
-        dh2 = dh.reshape(-1, dh.shape[-1])
+        dh2 = dh.reshape(-1, dh.shape[-1]).contiguous()               # (whatever layout dh arrives in: the same product, the same bits)
         onehot = F.one_hot(ids.reshape(-1), ctx.vocab).to(dh2.dtype)
         return None, split_k_weight_grad(onehot, dh2).to(dh.dtype)
 

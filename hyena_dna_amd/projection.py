@@ -159,6 +159,8 @@ class SplitKLinearFunc(torch.autograd.Function):
         wdt, bdt, dt = ctx.ptypes
         n, k = weight.shape
         dy2 = dy.reshape(-1, n)
+        if not dy2.is_contiguous():
+            dy2 = dy2.contiguous()                       # (a transposed view would pick other GEMM kernels: the gradients' bits must not depend on dy's layout)
         x2 = x.reshape(-1, k)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
@@ -167,7 +169,7 @@ class SplitKLinearFunc(torch.autograd.Function):
             dw = _castcache.wgrad_out(split_k_weight_grad(dy2, x2), wdt, dt)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             from . import _lib
-            db = _lib.colsum(dy2.contiguous()) if dy2.is_cuda else dy2.sum(0, dtype=torch.float32)
+            db = _lib.colsum(dy2) if dy2.is_cuda else dy2.sum(0, dtype=torch.float32)
             db = _castcache.wgrad_out(db, bdt, dt if dt is not None else dy.dtype)
         return dx, dw, db, None
 
@@ -270,6 +272,10 @@ class InProjCMFunc(torch.autograd.Function):
         from . import _lib
         u2, weight = ctx.saved_tensors
         dxT = _lib.as_cm(dxT)
+        if _lib.cm_matrix(dxT) is None:
+            # a caller's view whose sequences are pitched one by one (never the mixer's own dxT): repacked, so that the weight gradient is summed as
+            # ONE (C, B L) product whatever layout the gradient arrives in -- per-sequence products add the same terms in another order
+            dxT = dxT.contiguous()
         du = dw = None
         if ctx.needs_input_grad[0]:
             du = pm_from_cm(dxT, weight).view(ctx.ushape)

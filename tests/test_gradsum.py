@@ -71,8 +71,11 @@ def test_side_table_only_answers_for_the_very_tensor():
 
 
 def test_lm_gradients_with_and_without_the_side_table(emu_backend, monkeypatch):
-    """the model's bias gradients come out the same (fp32 summation order apart) whether out_proj's / fc2's backward takes the offered sums or makes its own pass"""
+    """the model's bias gradients of out_proj / fc2 are column sums of dx0 whether the backward takes the offered sums or makes its own pass: either
+    way each is held to the float64 column sums of that very tensor within the bound tests/block_local.py holds add_norm_bwd's np = 3 column sums to,
+    the parameter's .grad is that sum rounded to the parameter's type, and every other gradient is the same bits with the table on and off"""
     import hyena_dna_amd.lm as LM
+    from tests import block_local as BL
     L, D = 128, 128
     layer = dict(l_max=L + 2, order=2, filter_order=64, emb_dim=5, short_filter_order=3, modulate=True, w=10)
     torch.manual_seed(0)
@@ -80,17 +83,38 @@ def test_lm_gradients_with_and_without_the_side_table(emu_backend, monkeypatch):
                       pad_vocab_size_multiple=8, fused_dropout_add_ln=True, residual_in_fp32=True).to(torch.bfloat16)
     ids = torch.randint(7, 11, (2, L))
     tgt = torch.roll(ids, -1, 1)
-    params = [p for p in m.parameters() if p.requires_grad]
+    named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
+    params = [p for _, p in named]
+    sums, real = [], emu_backend.colsum
+
+    def colsum(x2):
+        out = real(x2)
+        sums.append((x2.detach().clone(), out.detach().clone()))
+        return out
+    monkeypatch.setattr(emu_backend, "colsum", colsum)
     res = {}
     for on in (True, False):
         monkeypatch.setattr(_gradsum, "ENABLED", on)
         _gradsum.reset()
+        del sums[:]
         h0 = _gradsum.stats()["hits"]
         loss = m.loss(ids, tgt)
-        res[on] = (loss.item(), torch.autograd.grad(loss, params, allow_unused=True), _gradsum.stats()["hits"] - h0)
+        res[on] = (loss.item(), torch.autograd.grad(loss, params, allow_unused=True), _gradsum.stats()["hits"] - h0, list(sums))
     assert res[True][2] >= 3 and res[False][2] == 0, (res[True][2], res[False][2])      # out_proj + fc2 of two layers (the last block's fc2 feeds the final norm)
     assert res[True][0] == res[False][0]
-    for (n, _), a, b in zip(m.named_parameters(), res[True][1], res[False][1]):
+    for on in (True, False):
+        assert len(res[on][3]) == 4                                # out_proj.bias and fc2.bias of two layers
+        for x2, cs in res[on][3]:
+            x64 = x2.double()
+            S = x64.abs().sum(0)
+            bound = BL.sum_bound(S, torch.zeros_like(S), BL.blk_depth(x2.shape[0]), 0)
+            assert cs.dtype == torch.float32 and ((cs.double() - x64.sum(0)).abs() <= bound).all(), (on, tuple(x2.shape))
+    for i, ((n, p), a, b) in enumerate(zip(named, res[True][1], res[False][1])):
         assert (a is None) == (b is None)
-        if a is not None:
-            assert torch.allclose(a.float(), b.float(), rtol=2e-2, atol=1e-3), n
+        if a is None:
+            continue
+        if n.endswith("out_proj.bias") or n.endswith("fc2.bias"):
+            for on, g in ((True, a), (False, b)):
+                assert any(torch.equal(g, cs.to(g.dtype)) for _, cs in res[on][3]), (n, on, "is not a column sum rounded to the parameter's type")
+        else:
+            assert torch.equal(a, b), n
