@@ -643,8 +643,12 @@ __global__ void __launch_bounds__(64) decode_advance_block_kernel(int* pos, int 
 // One wavefront per logit row (V <= 64: lane i holds logit i); workgroup = one wavefront, rows beyond the grid by a grid-stride loop.  The
 // row's column c = col[b] and its done flag live in device memory, like the decode positions: one captured graph serves every token, and
 // the token goes straight into the graph's static id buffer (`next`) and into column c of the preallocated sequence tensor.
-//   rank     r_i = #{ j < Vlive : l_j > l_i, or l_j == l_i and j < i }       (a permutation of 0 .. Vlive - 1; -inf logits rank by index)
-//   greedy   top_k <= 1: the token of rank 0; nothing random is drawn
+//   rank     r_i = #{ j < Vlive : j comes before i }: a NaN before every number, among NaNs the lower index first; among numbers l_j > l_i, or
+//            l_j == l_i and j < i (torch.sort(l, descending=True, stable=True): a permutation of 0 .. Vlive - 1 for EVERY input; equal values,
+//            -inf among them, rank by index)
+//   greedy   top_k <= 1: the token of rank 0 (torch.argmax); nothing random is drawn
+//   total    a row whose rank-0 logit is not finite (a NaN, a +inf, or -inf: every live logit is -inf) emits its rank-0 token whatever top_k,
+//            top_p and T are (its masses would be NaN); u is drawn and reported as for any other row
 //   top-k    keep r_i < min(top_k, Vlive); p_i = exp((l_i - max l) / T) in fp32, summed IN RANK ORDER (every lane runs the same serial scan
 //            over LDS: the sums do not depend on lane count or reduction shape)
 //   top-p    the kept tokens whose preceding kept mass is < top_p Z: a prefix in rank order (the masses are >= 0), never empty
@@ -697,7 +701,8 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_kernel(SampleArgs a) {
         int r = 0;
         for (int j = 0; j < a.Vlive; ++j) {
             const float lj = sl[j];
-            r += (lj > l || (lj == l && j < i)) ? 1 : 0;
+            const bool first = lj != lj ? (l == l || j < i) : (lj > l || (lj == l && j < i));   // (a NaN l: both comparisons are false)
+            r += first ? 1 : 0;
         }
         if (live) {
             ss[r] = l;
@@ -722,13 +727,18 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_kernel(SampleArgs a) {
             philox4x32_10((unsigned)c, (unsigned)b, (unsigned)seed, (unsigned)(seed >> 32), rnd);
             const float u = (float)(rnd[0] >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
             const float target = u * kept;
-            tok = si[nk - 1];
-            float acc = 0.f;
-            for (int q = 0; q < nk; ++q) {
-                acc += sp[q];
-                if (acc > target) {
-                    tok = si[q];
-                    break;
+            const float top = ss[0];
+            if (!(top - top == 0.f)) {                           // rank 0 is NaN or +-inf: sp, Z and nk mean nothing
+                tok = si[0];
+            } else {
+                tok = si[nk - 1];
+                float acc = 0.f;
+                for (int q = 0; q < nk; ++q) {
+                    acc += sp[q];
+                    if (acc > target) {
+                        tok = si[q];
+                        break;
+                    }
                 }
             }
             if (i == 0 && a.u_out != nullptr) a.u_out[b] = u;

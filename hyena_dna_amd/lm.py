@@ -380,7 +380,10 @@ class GenerationMixin:
         ``seed`` (the draws are a pure function of (seed, row, column); None: one seed from torch's generator per call) and ``vocab_size``
         (logit columns from there on, the padded vocabulary, are never chosen).  None: ``"device"`` when any of those four is given, else
         ``"torch"``.  ``stop_check_every=K > 0`` reads on the host every K tokens whether every row has finished and stops early (0: the
-        loop never reads anything back).
+        loop never reads anything back).  The device sampler is a total function of its logits (it ends a captured graph and cannot raise):
+        a NaN ranks before every number, the first NaN first (``torch.argmax``, ``torch.sort(descending=True, stable=True)``), and a row
+        whose top-ranked logit is NaN or infinite emits that token whatever ``top_k``, ``top_p`` and ``temperature`` are -- always an id
+        below ``vocab_size``; ``scores`` keep the NaN for the caller to see.
 
         ``num_return_sequences=n > 1``: n continuations of every prompt.  ``input_ids`` (G, P) -> ``sequences`` (G n, max_length), row
         g n + j being sample j of prompt g; ``scores`` are those of a batch of G n rows.  Needs ``use_cache=True``: the prefill runs once

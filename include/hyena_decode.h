@@ -112,12 +112,16 @@ int hyena_decode_post_block_fan(const float* part, const void* vgr, const float*
  *   c outside [0, ncols): parked, nothing of the row is read or written;  done[b] != 0: next[b ldn] = pad and nothing else;  otherwise
  *   scores[b, c, i] = l_i / T for i < V (scores (B, ncols, V) fp32 or NULL; T = max(temperature, 1e-6)), the token is drawn, and
  *   seq[b, c] = next[b ldn] = tok, col[b] = c + 1, done[b] = 1 if tok == eos (eos < 0: none).
- * The draw, with rank r_i = #{ j < Vlive : l_j > l_i, or l_j == l_i and j < i }: top_k <= 1 takes rank 0 (the maximum, lowest index on a tie;
- * top_p and the seed do not matter).  Otherwise keep r_i < min(top_k, Vlive), p_i = exp((l_i - max l) / T) in fp32 over them and Z their sum;
+ * The draw is a total function of the logits.  Rank r_i = #{ j < Vlive : j comes before i }, where a NaN comes before every number and, among
+ * NaNs, the lower index first; among numbers j comes before i iff l_j > l_i, or l_j == l_i and j < i.  That is the order of
+ * torch.sort(l, descending=True, stable=True), and the ranks are a permutation of 0 .. Vlive - 1 for every input.  top_k <= 1 takes rank 0
+ * (torch.argmax: the first NaN, else the maximum, lowest index on a tie; top_p and the seed do not matter).  A row whose rank-0 live logit is
+ * not finite -- a NaN, a +inf, or -inf, which means every live logit is -inf -- emits its rank-0 token whatever top_k, top_p and T are; u is
+ * drawn and reported, and col, done, eos, pad and scores (l / T verbatim, the NaN included) behave as for any other row.  Otherwise keep r_i < min(top_k, Vlive), p_i = exp((l_i - max l) / T) in fp32 over them and Z their sum;
  * keep token i iff the kept mass ranked strictly before it is < top_p Z (0 < top_p <= 1); with u = (w >> 8) 2^-24, w word 0 of
  * Philox4x32-10(counter (c, b, 0, 0), key *seed (low, high word)), the token is the kept one of smallest rank whose inclusive cumulative
  * mass exceeds u Z' (Z' the kept mass), else the last kept one.  u_out (B,) fp32 or NULL receives u.  `seed` is a DEVICE pointer to one
- * 64-bit word.  Logits are finite or -inf, at least one finite among the live ones.  Bad arguments (a null required pointer, V > 64, Vlive
+ * 64-bit word.  The emitted token is always in [0, Vlive).  Bad arguments (a null required pointer, V > 64, Vlive
  * outside [1, V], top_p outside (0, 1], an unknown dtype, ldl < V, lds < ncols) return HYENA_ERR_BAD_ARG before anything is launched. */
 int hyena_decode_sample(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
                         const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,

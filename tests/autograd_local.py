@@ -820,14 +820,9 @@ def _plain_name(n):
     return n.replace(".layer.", ".")
 
 
-def lm_run(_lib, dev, cfg, ck=(False, False), freeze="all_trainable", gradsum=True, B=2):
-    """one training step's loss and parameter gradients (by name, ``.layer.`` removed) of a 2-layer HyenaDNALM built from torch seed 0 and run
-    from torch seed 1, with the Functions that ran and every hit of the _gradsum side table (the tensor asked about, the sums handed over)"""
+def lm_build(dev, cfg, ck=(False, False), freeze="all_trainable", B=2):
+    """the 2-layer HyenaDNALM of lm_run (torch seed 0, biases given values, ``freeze`` applied) in train mode, its ids and targets"""
     import hyena_dna_amd.lm as LM
-    from hyena_dna_amd import _castcache, _gradsum
-    key = (cfg, ck, freeze, gradsum, str(dev), _lib._backend.name)
-    if key in _lm_cache:
-        return _lm_cache[key]
     D, ac, order, p = cfg
     L = LM_LEN
     torch.manual_seed(0)
@@ -843,7 +838,19 @@ def lm_run(_lib, dev, cfg, ck=(False, False), freeze="all_trainable", gradsum=Tr
     for n, q in m.named_parameters():
         q.requires_grad_(bool(want(_plain_name(n))))
     ids = torch.randint(7, 11, (B, L), generator=torch.Generator().manual_seed(3)).to(dev)
-    tgt = torch.roll(ids, -1, 1)
+    return m, ids, torch.roll(ids, -1, 1)
+
+
+def lm_run(_lib, dev, cfg, ck=(False, False), freeze="all_trainable", gradsum=True, B=2):
+    """one training step's loss and parameter gradients (by name, ``.layer.`` removed) of a 2-layer HyenaDNALM built from torch seed 0 and run
+    from torch seed 1, with the Functions that ran and every hit of the _gradsum side table (the tensor asked about, the sums handed over)"""
+    import hyena_dna_amd.lm as LM
+    from hyena_dna_amd import _castcache, _gradsum
+    key = (cfg, ck, freeze, gradsum, str(dev), _lib._backend.name)
+    if key in _lm_cache:
+        return _lm_cache[key]
+    D, ac, order, p = cfg
+    m, ids, tgt = lm_build(dev, cfg, ck, freeze, B)
     takes, real_take, was = [], _gradsum.take, _gradsum.ENABLED
 
     def take(x2):

@@ -7,7 +7,10 @@ case's draws -- asserted): a draw whose u Z' lies within relative 1e-5 of a cumu
 top_p < 1 -- whose nucleus has a boundary within 1e-6 Z of top_p Z.  (At top_p = 1 the nucleus test reads "mass before < Z": it can only fail
 for trailing tokens whose mass fp32 absorbs, below 64 * 2^-24 Z = 4e-6 Z in total; dropping them moves Z' by that relative amount, so a draw
 can change only where u Z' already lies within 1e-5 of a boundary.  Counting the 1e-6 Z rule there as well would throw out every row whose
-smallest token has p < 1e-6 Z -- four in ten rows of 64 N(0, 2^2) logits at T = 0.7 -- for no difference in the outcome.)"""
+smallest token has p < 1e-6 Z -- four in ten rows of 64 N(0, 2^2) logits at T = 0.7 -- for no difference in the outcome.)
+
+The sampler is a total function of its logits: a NaN ranks before every number (torch's stable descending sort), and a row whose rank-0 logit is
+NaN or infinite emits its rank-0 token whatever the settings -- deterministic, so such a row is never left out (section 2b, case_nonfinite)."""
 import functools
 
 import numpy as np
@@ -41,14 +44,25 @@ def reference(l, Vlive, T, top_k, top_p, u):
     B, V = l.shape
     j = np.arange(V)
     live = j < Vlive
-    gt = (l[:, None, :] > l[:, :, None]) | ((l[:, None, :] == l[:, :, None]) & (j[None, None, :] < j[None, :, None]))      # [b, i, j]: j before i
+    lower = j[None, None, :] < j[None, :, None]
+    nan = np.isnan(l)
+    gt = np.where(nan[:, None, :], ~nan[:, :, None] | lower,                     # [b, i, j]: j before i -- a NaN before every number, the lower
+                  (l[:, None, :] > l[:, :, None]) | ((l[:, None, :] == l[:, :, None]) & lower))     # NaN first; numbers: greater, then lower
     r = (gt & live[None, None, :]).sum(-1)                                       # (B, V) rank of token i among the live ones
+    assert (np.sort(r[:, :Vlive], 1) == j[None, :Vlive]).all()                   # a permutation, whatever the row holds
     by_rank = np.zeros((B, Vlive), dtype=np.int64)
     rows = np.arange(B)[:, None].repeat(Vlive, 1)
     by_rank[rows, r[:, :Vlive]] = j[None, :Vlive]
     if top_k <= 1:
         return by_rank[:, 0], np.zeros(B, dtype=bool)
     k = min(top_k, Vlive)
+    total = ~np.isfinite(l[rows[:, 0], by_rank[:, 0]])                           # rank 0 is NaN, +inf or -inf: the row emits its rank-0 token
+    if total.any():
+        tok, left_out = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=bool)
+        tok[total] = by_rank[total, 0]
+        if not total.all():
+            tok[~total], left_out[~total] = reference(l[~total], Vlive, T, top_k, top_p, u[~total])
+        return tok, left_out
     ls = np.take_along_axis(l, by_rank, 1)[:, :k]                                # kept logits in rank order
     with np.errstate(invalid="ignore"):
         p = np.exp((ls - ls[:, :1]) / T)
@@ -169,6 +183,131 @@ def case_greedy_ties(_lib, dev, dtype):
         l[b, first[b]:first[b] + 1 + b % 3] = 2.5                               # one, two or three equal maxima
     out = run_kernel(_lib, dev, l.to(dtype), torch.zeros(B_CASE, dtype=torch.int32), SEED, 1.0, 1, 0.5, V)
     assert torch.equal(out["seq"][:, 0], first) and torch.isnan(out["u"]).all()  # (greedy draws nothing)
+
+
+# ---- 2b. non-finite logits: the sampler is a total function ----------------------------------------------------------------------------------
+NF_SHAPES = [(12, 12), (16, 12), (64, 64), (64, 60)]
+NF_KINDS = ("one NaN off the maximum", "two NaNs", "all live NaN", "one +inf", "two +inf", "NaN and +inf", "all live -inf", "NaN in a dead column")
+SMP_MAX_GRID = 1 << 16                                                           # csrc/decode_kernels.h: rows from there on share a workgroup with row b - 2^16
+
+
+def plant_nonfinite(l, Vlive):
+    """row b gets NF_KINDS[b % 8], at columns that move with b // 8; kind 7 (nothing planted where Vlive == V) must behave as a clean row"""
+    l = l.clone()
+    V = l.shape[1]
+    nan, inf = float("nan"), float("inf")
+    for b in range(l.shape[0]):
+        kind, c = b % 8, (b // 8) % Vlive
+        if kind == 0:
+            l[b, (int(l[b, :Vlive].float().argmax()) + 1) % Vlive] = nan
+        elif kind == 1:
+            l[b, c], l[b, (c + 5) % Vlive] = nan, nan
+        elif kind == 2:
+            l[b, :Vlive] = nan
+        elif kind == 3:
+            l[b, (c + 2) % Vlive] = inf
+        elif kind == 4:
+            l[b, c], l[b, (c + 7) % Vlive] = inf, inf
+        elif kind == 5:
+            l[b, c], l[b, (c + (1 if (b // 8) % 2 else Vlive - 1)) % Vlive] = inf, nan      # the NaN after the +inf, or before it
+        elif kind == 6:
+            l[b, :Vlive] = -inf
+        elif Vlive < V:
+            l[b, Vlive + (b // 8) % (V - Vlive)] = nan
+    return l
+
+
+def _same_with_nans(a, b):
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(a[~torch.isnan(a)], b[~torch.isnan(b)])
+
+
+def case_nonfinite(_lib, dev, V, Vlive, dtype):
+    """256 rows, NF_KINDS by row index modulo 8, against the restatement: the planted rows exactly and without exception, the clean ones (kind 7)
+    as in case_kernel_vs_reference and bitwise what the call without any planted row gives them"""
+    base = make_logits(V, Vlive, dtype, 100 * V + Vlive)
+    logits = plant_nonfinite(base, Vlive)
+    col = make_cols(V + Vlive)
+    l64 = logits.double().numpy()
+    livecol = (col >= 0) & (col < NCOLS)
+    cc = col.clamp(0, NCOLS - 1).long()
+    u = uniforms(SEED, B_CASE, NCOLS)[np.arange(B_CASE), cc.numpy()]
+    rows = torch.arange(B_CASE)
+    clean = rows % 8 == 7
+    # the restatement's order is torch's: stable descending sort, and greedy is torch.argmax
+    order = torch.sort(logits[:, :Vlive], descending=True, stable=True, dim=1).indices
+    greedy, _ = reference(l64, Vlive, 1.0, 1, 1.0, u)
+    assert torch.equal(torch.from_numpy(greedy), order[:, 0]) and torch.equal(order[:, 0], torch.argmax(logits[:, :Vlive], dim=1))
+    eos = 3
+    for top_k in (1, 4, Vlive):
+        for top_p in (1.0, 0.3):
+            for T in (1.0, 0.7):
+                T32 = float(np.float32(T))
+                want, left_out = reference(l64, Vlive, T32, top_k, float(np.float32(top_p)), u)
+                assert not (left_out & ~clean.numpy()).any()                     # planted rows are deterministic: none may be left out
+                top = torch.from_numpy(l64)[rows, order[:, 0]]
+                assert bool((torch.from_numpy(want)[~torch.isfinite(top)] == order[:, 0][~torch.isfinite(top)]).all())
+                assert not torch.isfinite(top[rows % 8 < 7]).any() and torch.isfinite(top[clean]).all()
+                n_left, n_clean = int((left_out & livecol.numpy()).sum()), int((livecol & clean).sum())
+                print(f"V={V} Vlive={Vlive} {dtype} top_k={top_k} top_p={top_p} T={T}: {n_left} of {n_clean} clean draws left out")
+                assert n_left <= 0.01 * n_clean
+                out = run_kernel(_lib, dev, logits, col, SEED, T, top_k, top_p, Vlive, eos=eos)
+                got = out["seq"][rows, cc]
+                assert bool(((got >= 0) & (got < Vlive))[livecol].all()), got[livecol & ((got < 0) | (got >= Vlive))][:8].tolist()
+                bad = (got != torch.from_numpy(want)) & livecol & ~torch.from_numpy(left_out)
+                assert not bad.any(), (top_k, top_p, T, bad.nonzero()[:8, 0].tolist(), got[bad][:8].tolist(), want[bad.numpy()][:8].tolist())
+                # the sentinel rules: one element of seq per live row, next the same, col + 1, done on eos, u drawn unless greedy, scores = l / T
+                assert torch.equal(out["nxt"][livecol], got[livecol]) and bool((out["nxt"][~livecol] == -9).all())
+                changed = out["seq"] != -7
+                assert torch.equal(changed.sum(1), livecol.long()) and bool(changed[rows[livecol], cc[livecol]].all())
+                assert torch.equal(out["col"], col + livecol.int()) and torch.equal(out["done"], (livecol & (got == eos)).int())
+                if top_k <= 1:
+                    assert torch.isnan(out["u"]).all()
+                else:
+                    assert torch.equal(out["u"][livecol].double(), torch.from_numpy(u)[livecol]) and torch.isnan(out["u"][~livecol]).all()
+                s = out["scores"][rows, cc].double()[livecol]
+                ref = torch.from_numpy(l64 / T32)[livecol]
+                fin = torch.isfinite(ref)
+                assert _same_with_nans(s[~fin], ref[~fin]) and ((s[fin] - ref[fin]).abs() <= 2.0 ** -23 * ref[fin].abs()).all()
+                mask = torch.zeros(B_CASE, NCOLS, dtype=torch.bool)
+                mask[rows[livecol], cc[livecol]] = True
+                assert torch.isnan(out["scores"][~mask]).all()
+                # the clean rows among planted ones, and with a NaN in a dead column: the bits of the call that holds no planted row
+                alone = run_kernel(_lib, dev, base, col, SEED, T, top_k, top_p, Vlive, eos=eos, want_scores=False)
+                assert torch.equal(alone["seq"][clean], out["seq"][clean]) and torch.equal(alone["done"][clean], out["done"][clean])
+
+
+def case_nonfinite_grid_stride(_lib, dev, dtype):
+    """B = SMP_MAX_GRID + 256: workgroup b runs planted row b, then the clean row b + 2^16 with whatever the planted row left in LDS.  The clean
+    rows' tokens are those of the call in which the planted rows are parked (the draw depends on the row index, so the rows keep their places)"""
+    from tests.test_block_emu import _philox4x32_10
+    V, Vlive, n = 16, 12, B_CASE
+    B = SMP_MAX_GRID + n
+    base = make_logits(V, Vlive, dtype, 7)
+    logits = torch.zeros(B, V, dtype=dtype)
+    logits[:n] = plant_nonfinite(base, Vlive)
+    logits[SMP_MAX_GRID:] = base
+    head, tail = slice(0, n), slice(SMP_MAX_GRID, B)
+    col = torch.full((B,), -1, dtype=torch.int32)                               # rows n .. 2^16 - 1 stay parked
+    col[tail] = 2
+    col_planted = col.clone()
+    col_planted[head] = 5
+    k0, k1 = _words(SEED)
+    u_head = np.array([(_philox4x32_10(5, b, k0, k1)[0] >> 8) * 2.0 ** -24 for b in range(n)])
+    u_tail = np.array([(_philox4x32_10(2, b, k0, k1)[0] >> 8) * 2.0 ** -24 for b in range(SMP_MAX_GRID, B)])
+    for top_k, top_p in ((1, 1.0), (4, 0.3), (Vlive, 1.0)):
+        T32 = float(np.float32(0.7))
+        want_h, left_h = reference(logits[head].double().numpy(), Vlive, T32, top_k, float(np.float32(top_p)), u_head)
+        want_t, left_t = reference(logits[tail].double().numpy(), Vlive, T32, top_k, float(np.float32(top_p)), u_tail)
+        planted = np.arange(n) % 8 < 7
+        assert not left_h[planted].any() and int(left_t.sum()) <= 0.01 * n
+        alone = run_kernel(_lib, dev, logits, col, SEED, 0.7, top_k, top_p, Vlive, want_scores=False)
+        both = run_kernel(_lib, dev, logits, col_planted, SEED, 0.7, top_k, top_p, Vlive, want_scores=False)
+        assert bool((alone["seq"][:SMP_MAX_GRID] == -7).all()) and bool((both["seq"][n:SMP_MAX_GRID] == -7).all())
+        assert torch.equal(both["seq"][tail], alone["seq"][tail]) and torch.equal(both["nxt"][tail], alone["nxt"][tail])
+        got_t, got_h = both["seq"][tail, 2], both["seq"][head, 5]
+        assert bool(((got_t >= 0) & (got_t < Vlive)).all()) and bool(((got_h >= 0) & (got_h < Vlive)).all())
+        assert torch.equal(got_t[~left_t], torch.from_numpy(want_t)[~left_t]), (top_k, top_p)
+        assert torch.equal(got_h[planted], torch.from_numpy(want_h)[planted]), (top_k, top_p)
 
 
 # ---- 3. the distribution of the draws ----------------------------------------------------------------------------------------------------------

@@ -34,6 +34,17 @@ def test_kernel_vs_fp64_restatement(sample_emu, V, Vlive, dtype):
 
 
 @pytest.mark.parametrize("dtype", DS.DTYPES)
+@pytest.mark.parametrize("V,Vlive", DS.NF_SHAPES)
+def test_nonfinite_logits_rank_first_and_emit_rank_0(sample_emu, V, Vlive, dtype):
+    DS.case_nonfinite(sample_emu, DEV, V, Vlive, dtype)
+
+
+@pytest.mark.parametrize("dtype", DS.DTYPES)
+def test_clean_rows_after_nonfinite_rows_in_the_grid_stride_loop(sample_emu, dtype):
+    DS.case_nonfinite_grid_stride(sample_emu, DEV, dtype)
+
+
+@pytest.mark.parametrize("dtype", DS.DTYPES)
 def test_greedy_takes_the_lowest_index_of_equal_maxima(sample_emu, dtype):
     DS.case_greedy_ties(sample_emu, DEV, dtype)
 

@@ -21,6 +21,17 @@ def test_kernel_vs_fp64_restatement(gpu_lib, V, Vlive, dtype):
 
 
 @pytest.mark.parametrize("dtype", DS.DTYPES)
+@pytest.mark.parametrize("V,Vlive", DS.NF_SHAPES)
+def test_nonfinite_logits_rank_first_and_emit_rank_0(gpu_lib, V, Vlive, dtype):
+    DS.case_nonfinite(gpu_lib, DEV, V, Vlive, dtype)
+
+
+@pytest.mark.parametrize("dtype", DS.DTYPES)
+def test_clean_rows_after_nonfinite_rows_in_the_grid_stride_loop(gpu_lib, dtype):
+    DS.case_nonfinite_grid_stride(gpu_lib, DEV, dtype)
+
+
+@pytest.mark.parametrize("dtype", DS.DTYPES)
 def test_greedy_takes_the_lowest_index_of_equal_maxima(gpu_lib, dtype):
     DS.case_greedy_ties(gpu_lib, DEV, dtype)
 
