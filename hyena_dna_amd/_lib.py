@@ -197,6 +197,18 @@ def lib():
                          (L.hyena_decode_post_block, L.hyena_decode_post), (L.hyena_decode_pre_block_fan, L.hyena_decode_pre_fan),
                          (L.hyena_decode_conv_block_fan, L.hyena_decode_conv_fan), (L.hyena_decode_post_block_fan, L.hyena_decode_post_fan)):
             blk.restype, blk.argtypes = c_int, one.argtypes[:-1] + [c_int, c_void_p]
+        # lookahead carry: the history's share of the next W outputs, and the step on [base, t]
+        L.hyena_decode_carry_partial_floats.restype = c_size_t
+        L.hyena_decode_carry_partial_floats.argtypes = [c_int, c_int, c_int, c_int]
+        L.hyena_decode_carry.restype = c_int
+        L.hyena_decode_carry.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p]
+        L.hyena_decode_conv_la.restype = c_int
+        L.hyena_decode_conv_la.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p]
+        L.hyena_decode_post_la.restype = c_int
+        L.hyena_decode_post_la.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                           c_int, c_int, c_int, c_void_p]
         L.hyena_decode_sample.restype = c_int
         L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
@@ -1030,6 +1042,51 @@ def decode_post_block_fan(part, hist_r, fb, x0, z, pos, fan, Lcap, S):
         check(lib().hyena_decode_post_block_fan(part.data_ptr(), hist_r.data_ptr(), None if fb is None else fb.data_ptr(), x0.data_ptr(),
                                                 z.data_ptr(), pos.data_ptr(), B, int(fan), D, int(Lcap), int(S), ldr, T,
                                                 dtype_code(hist_r.dtype), _backend.stream(z.device)))
+
+
+# ---- the lookahead carry (hyena_decode_carry, _conv_la, _post_la): carry (B, W, D) fp32 holds the share of outputs base ... base + W - 1 that
+# comes from the history below base; pos and base one-int device tensors; the plain cache only ----
+def decode_carry_partials(B, D, Lcap, W, device):
+    return torch.empty(lib().hyena_decode_carry_partial_floats(int(B), int(D), int(Lcap), int(W)), dtype=torch.float32, device=device)
+
+
+def _carry(carry, base, B, D):
+    assert carry.dtype == torch.float32 and carry.dim() == 3 and carry.is_contiguous() and carry.shape[0] >= B and carry.shape[2] == D
+    assert base.dtype == torch.int32 and base.numel() == 1
+    return carry.shape[1]
+
+
+def decode_carry(k, hist, part, carry, pos, base, B, Lcap):
+    """carry[b, j, d] = sum_{s < t0} k[d, t0 + j - s] hist[b, d, s] for the W = carry.shape[1] outputs from t0 = pos on; then base = t0"""
+    _require_gpu(k, "k")
+    _, D, lda = _hist(hist)
+    W = _carry(carry, base, B, D)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_carry(k.data_ptr(), k.stride(0), hist.data_ptr(), part.data_ptr(), carry.data_ptr(), pos.data_ptr(),
+                                       base.data_ptr(), int(B), D, int(Lcap), lda, W, dtype_code(hist.dtype), _backend.stream(k.device)))
+
+
+def decode_conv_la(k, hist, part, pos, base, B, W, Lcap):
+    """decode_conv over s in [base, t] only: part (2, B, D), slot x for chunk base // 8192 + x"""
+    _require_gpu(k, "k")
+    _, D, lda = _hist(hist)
+    assert k.dtype == torch.float32 and k.stride(1) == 1 and k.shape[0] == D and part.numel() >= 2 * int(B) * D
+    with _backend.guard(k.device):
+        check(lib().hyena_decode_conv_la(k.data_ptr(), k.stride(0), hist.data_ptr(), part.data_ptr(), pos.data_ptr(), base.data_ptr(), int(B), D,
+                                         int(Lcap), lda, int(W), dtype_code(hist.dtype), _backend.stream(k.device)))
+
+
+def decode_post_la(part, carry, hist, fb, x0, z, pos, base, B, Lcap):
+    """z (B, D) = round(round(carry[:, t - base] + the live partials + fb hist[:, :, t]) * x0); advances pos"""
+    _require_gpu(z, "z")
+    _, D, lda = _hist(hist)
+    W = _carry(carry, base, B, D)
+    assert z.dtype == hist.dtype and z.is_contiguous()
+    with _backend.guard(z.device):
+        check(lib().hyena_decode_post_la(part.data_ptr(), carry.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(),
+                                         x0.data_ptr(), z.data_ptr(), pos.data_ptr(), base.data_ptr(), int(B), D, int(Lcap), lda, W,
+                                         dtype_code(hist.dtype), _backend.stream(z.device)))
 
 
 # ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------

@@ -341,6 +341,56 @@ int hyena_decode_post_block(const float* part, const void* vg, const float* fb, 
     return hyena_decode_post_block_fan(part, vg, fb, x0, z, pos, B, 1, D, Lcap, 0, lda, T, dtype, stream);
 }
 
+// ---- lookahead carry (decode_carry_kernel, decode_conv_la_kernel, decode_post_la_kernel): the plain cache only -------------------------------
+size_t hyena_decode_carry_partial_floats(int B, int D, int Lcap, int W) {
+    if (B < 1 || D < 1 || Lcap < 1 || Lcap > DEC_MAX_L || !dec_block_T_ok(W)) return 0;
+    return (size_t)dec_chunks(Lcap) * B * W * D;
+}
+
+int hyena_decode_carry(const float* k, int ldk, const void* vg, float* part, float* carry, const int* pos, int* base, int B, int D, int Lcap,
+                       int lda, int W, int dtype, void* stream) {
+    if (!dec_block_T_ok(W) || k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || carry == nullptr ||
+        pos == nullptr || base == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || D > 65535 || (long)B * D > (1L << 30) / DEC_TMAX)
+        return HYENA_ERR_BAD_ARG;
+    DecLaArgs a;
+    static_cast<DecArgs&>(a) = dec_args();
+    a.k = k; a.vg = const_cast<void*>(vg); a.part = part; a.carry = carry; a.pos = const_cast<int*>(pos); a.base = base; a.W = W;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_carry_kernel, dim3(dec_chunks(Lcap), D), DEC_THREADS, (DEC_KLDS_BLOCK + DEC_RED_BLOCK) * sizeof(float));
+    if (hy_launch_error()) return HYENA_ERR_LAUNCH;
+    HY_LAUNCH(decode_carry_reduce_kernel, dim3((unsigned)(((size_t)B * W * D + DEC_THREADS - 1) / DEC_THREADS)), dim3(DEC_THREADS), 0, stream, a);
+    if (hy_launch_error()) return HYENA_ERR_LAUNCH;
+    HY_LAUNCH(decode_set_base_kernel, dim3(1), dim3(64), 0, stream, pos, base, Lcap);   // after every read of the position
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_conv_la(const float* k, int ldk, const void* vg, float* part, const int* pos, const int* base, int B, int D, int Lcap, int lda,
+                         int W, int dtype, void* stream) {
+    if (!dec_block_T_ok(W) || k == nullptr || !dec_aligned16(k) || ldk < Lcap || ldk % 4 != 0 || part == nullptr || pos == nullptr ||
+        base == nullptr || !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || D > 65535)
+        return HYENA_ERR_BAD_ARG;
+    DecLaArgs a;
+    static_cast<DecArgs&>(a) = dec_args();
+    a.k = k; a.vg = const_cast<void*>(vg); a.part = part; a.carry = nullptr; a.pos = const_cast<int*>(pos); a.base = const_cast<int*>(base);
+    a.W = W; a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda; a.ldk = ldk;
+    HY_DEC_DISPATCH(decode_conv_la_kernel, dim3(2, D), DEC_THREADS, (DEC_KLDS_LA + 8) * sizeof(float));
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_post_la(const float* part, const float* carry, const void* vg, const float* fb, const float* x0, void* z, int* pos,
+                         const int* base, int B, int D, int Lcap, int lda, int W, int dtype, void* stream) {
+    if (!dec_block_T_ok(W) || part == nullptr || carry == nullptr || x0 == nullptr || z == nullptr || pos == nullptr || base == nullptr ||
+        !dec_hist_ok(vg, B, D, Lcap, lda, dtype) || (long)B * D > (1L << 30) / DEC_TMAX)
+        return HYENA_ERR_BAD_ARG;
+    DecLaArgs a;
+    static_cast<DecArgs&>(a) = dec_args();
+    a.part = const_cast<float*>(part); a.carry = const_cast<float*>(carry); a.vg = const_cast<void*>(vg); a.fb = fb;
+    a.x0 = const_cast<float*>(x0); a.z = z; a.pos = pos; a.base = const_cast<int*>(base); a.W = W;
+    a.B = B; a.D = D; a.Lcap = Lcap; a.lda = lda;
+    HY_DEC_DISPATCH(decode_post_la_kernel, dim3(1), DEC_POST_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
 // ---- token sampling (decode_sample_kernel): one wavefront per logit row -------------------------------------------------------------------
 int hyena_decode_sample(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
                         const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,

@@ -11,7 +11,8 @@
 //   decode_post  the partials summed in chunk order, + fb vg_t, rounded to the I/O type where the forward rounds the convolution's output,
 //                times x0_t with cm_post_fwd's arithmetic -> z_t; then the position advances
 // The position t lives in device memory and all three kernels read it there: one captured graph serves every position.
-// Variants further down: one position per row (_rows), n continuations of one prompt (_fan), and T known positions per call (_block).
+// Variants further down: one position per row (_rows), n continuations of one prompt (_fan), T known positions per call (_block), and the
+// lookahead carry (_carry, _la): the history's share of the next W outputs taken once per W positions, so that a step reads W + 7 columns.
 //
 // The two streams of decode_conv run in opposite directions (vg forward in s, k backward), and the k stream is misaligned by t mod 4 words
 // relative to the vg stream.  The history is the operand that scales with B, so ITS loads stay aligned 16-byte vectors (8 elements per lane at
@@ -637,6 +638,192 @@ __global__ void __launch_bounds__(DEC_THREADS) decode_post_block_kernel(DecBlock
 __global__ void __launch_bounds__(64) decode_advance_block_kernel(int* pos, int T, int S, int Lcap) {
     const int t0 = pos[0];
     if (threadIdx.x == 0 && blockIdx.x == 0 && t0 >= S && t0 <= Lcap - T) pos[0] = t0 + T;
+}
+
+// ---- lookahead carry: the history's share of the next W outputs, taken ahead (C ABI: hyena_decode_carry, _conv_la, _post_la) --------------
+// The convolution is linear in the history, so with t0 the position at a refresh and t0 <= t < t0 + W
+//     y_t = carry[b, t - t0, c] + sum_{s = t0 .. t} k[c, t - s] vg[b, c, s] + fb[c] vg[b, c, t],   carry[b, j, c] = sum_{s < t0} k[c, t0 + j - s] vg[b, c, s]
+// One refresh streams the history once for W outputs that are not known yet (decode_conv_block_kernel's tiles and staged window: the W
+// outputs of a (row, channel) read the same history vectors); a step then reads the at most W + 7 columns from t0 on.
+//   decode_carry_kernel         grid (nchunks, D): part[chunk][b][j][d] for the chunks that start below t0, outputs j < min(W, Lcap - t0).  The
+//                               bound s < t0 is taken on the HISTORY VALUE (a column at or past t0 enters as an exact 0, whatever it
+//                               holds), not on the tap: tap t0 + j - s is live for the outputs j > s - t0 and dead for the others.
+//   decode_carry_reduce_kernel  one thread per (b, j, d): the ceil(t0 / DEC_CHUNK) partials in chunk order -> carry (B, W, D); t0 = 0 gives
+//                               exact zeros and no history is read
+//   decode_set_base_kernel      one thread, behind them on the stream: *base = t0
+//   decode_conv_la_kernel       grid (2, D): decode_conv_kernel with the lower bound lo = *base.  [lo, t] spans at most two chunks (W <=
+//                               DEC_TMAX), so workgroup (x, c) takes chunk lo / DEC_CHUNK + x into part[x][b][c]; vectors that end at or
+//                               below lo are skipped, columns below lo inside a vector meet a zero tap (they are real, finite history).
+//                               The same lanes, FMA order and wave sums as decode_conv_kernel: with lo = 0 the same partial, bit for bit.
+//   decode_post_la_kernel       ONE workgroup: carry[b, t - lo, d], then the live partials in chunk order, then decode_post_kernel's tail
+// A step parks (nothing is written, the position stays) when t is outside [0, Lcap) or t - lo outside [0, W), or lo is negative.  Every
+// branch around a barrier is taken on pos[0] / base[0], W and blockIdx: uniform across the workgroup.
+struct DecLaArgs : DecArgs {
+    float* carry;       // (B, W, D) fp32
+    int* base;          // the position of the last refresh (device memory)
+    int W;
+};
+
+enum { DEC_KLDS_LA = DEC_TMAX + 8 /* floats: a step's window is the taps 0 .. t - lo < W, rounded outwards to 4 words */ };
+
+__device__ __forceinline__ bool dec_la_valid(const DecLaArgs& a, int t, int lo) {
+    return t >= 0 && t < a.Lcap && lo >= 0 && lo <= t && t - lo < a.W;
+}
+
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_carry_kernel(DecLaArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS_BLOCK;                             // [2][DEC_TT][4]: wavefront sums, alternating by the parity of the trip
+    const int t0 = a.pos[0];
+    const int chunk = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const int s0 = chunk * DEC_CHUNK;
+    if (t0 < 0 || t0 >= a.Lcap || s0 >= t0) return;                      // (t0 = 0: no workgroup stays)
+    const int T = a.W < a.Lcap - t0 ? a.W : a.Lcap - t0;                 // the outputs that lie inside the cache
+    // ks[m] = k[c, jlo + m] as in decode_conv_block_kernel; zero past the last output's first tap (k has Lcap columns)
+    const int jlo = t0 - s0 - DEC_CHUNK + 1, jhi = t0 + T - 1 - s0;
+    const float* krow = a.k + (size_t)c * a.ldk;
+    for (int m = tid; m < DEC_KLDS_BLOCK; m += DEC_THREADS) {
+        const int j = jlo + m;
+        const bool ok = j >= 0 && j <= jhi;
+        const float kv = krow[ok ? j : 0];
+        ks[m] = ok ? kv : 0.f;
+    }
+    __syncthreads();
+    bool live[DEC_NV];
+    HY_UNROLL
+    for (int v = 0; v < DEC_NV; ++v) live[v] = s0 + (v * DEC_THREADS + tid) * DEC_V < t0;
+    int trip = 0;
+    for (int b = 0; b < a.B; ++b) {
+        const char* row = cm_row(a.vg, (size_t)b * a.D + c, a.lda, ES);
+        float x[DEC_NV][DEC_V];
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            HY_UNROLL
+            for (int e = 0; e < DEC_V; ++e) x[v][e] = 0.f;
+            if (live[v]) {                                                // (s + DEC_V <= lda: 8-aligned rows; s < t0 < Lcap)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)s * ES, 16), sizeof(raw));
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) {
+                    const float xv = Elem<DT>::dec(raw[e]);
+                    x[v][e] = s + e < t0 ? xv : 0.f;                      // the value is selected, not multiplied: s < t0 holds exactly
+                }
+            }
+        }
+        float* part = a.part + (((size_t)chunk * a.B + b) * a.W) * a.D + c;
+        int i0 = 0;
+        for (; T - i0 > 3 * DEC_TR; i0 += DEC_TT) {                       // decode_conv_block_kernel's tiling
+            float acc[DEC_TT];
+            dec_block_tile<DEC_TT>(x, live, ks, tid, i0, acc);
+            dec_block_reduce<DEC_TT>(acc, red + DEC_TT * 4 * (trip++ & 1), tid, i0, T, part, a.D);
+        }
+        for (; i0 < T; i0 += DEC_TR) {
+            float acc[DEC_TR];
+            dec_block_tile<DEC_TR>(x, live, ks, tid, i0, acc);
+            dec_block_reduce<DEC_TR>(acc, red + DEC_TT * 4 * (trip++ & 1), tid, i0, T, part, a.D);
+        }
+    }
+}
+
+// one thread per (b, j, d): grid ceil(B W D / DEC_THREADS).  Slots j >= Lcap - t0 are not written.
+__global__ void __launch_bounds__(DEC_THREADS) decode_carry_reduce_kernel(DecLaArgs a) {
+    const int t0 = a.pos[0];
+    const size_t idx = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x;
+    if (idx >= (size_t)a.B * a.W * a.D || t0 < 0 || t0 >= a.Lcap) return;
+    const int d = (int)(idx % a.D), j = (int)(idx / a.D % a.W), b = (int)(idx / a.D / a.W);
+    if (j >= a.Lcap - t0) return;
+    const int nc = (t0 + DEC_CHUNK - 1) / DEC_CHUNK;
+    float y = 0.f;
+    for (int ch = 0; ch < nc; ++ch) y += a.part[(((size_t)ch * a.B + b) * a.W + j) * a.D + d];
+    a.carry[idx] = y;
+}
+
+// one thread, after decode_carry_reduce_kernel on the same stream
+__global__ void __launch_bounds__(64) decode_set_base_kernel(const int* pos, int* base, int Lcap) {
+    const int t0 = pos[0];
+    if (threadIdx.x == 0 && blockIdx.x == 0 && t0 >= 0 && t0 < Lcap) base[0] = t0;
+}
+
+// grid (2, D): workgroup (x, c) covers chunk lo / DEC_CHUNK + x of channel c for every b
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_conv_la_kernel(DecLaArgs a) {
+    constexpr size_t ES = CmEs<DT>::V;
+    HY_SMEM(smem);
+    HY_LDS float* ks = HY_LDS_CAST(float, smem);
+    HY_LDS float* red = ks + DEC_KLDS_LA;                                // [2][4]: wavefront sums, alternating by row parity
+    const int t = a.pos[0], lo = a.base[0];
+    const int c = blockIdx.y, tid = threadIdx.x;
+    if (!dec_la_valid(a, t, lo)) return;
+    const int s0 = (lo / DEC_CHUNK + (int)blockIdx.x) * DEC_CHUNK;
+    if (s0 > t) return;
+    // stage the taps jmin .. t - max(s0, lo) (at most W of them), rounded outwards to 4 words, with aligned 16-byte loads
+    const int shi = s0 > lo ? s0 : lo;
+    const int jmin = t - s0 - DEC_CHUNK + 1 > 0 ? t - s0 - DEC_CHUNK + 1 : 0;
+    const int kb = jmin & ~3;
+    const int ngroups = (t - shi - kb) / 4 + 1;
+    const float* krow = a.k + (size_t)c * a.ldk;
+    for (int q = tid; q < ngroups; q += DEC_THREADS) {
+        float r[4];
+        __builtin_memcpy(r, krow + kb + 4 * q, sizeof(r));
+        HY_UNROLL
+        for (int e = 0; e < 4; ++e) ks[4 * q + e] = r[e];
+    }
+    __syncthreads();
+    for (int b = 0; b < a.B; ++b) {
+        const char* row = cm_row(a.vg, (size_t)b * a.D + c, a.lda, ES);
+        float acc = 0.f;
+        HY_UNROLL
+        for (int v = 0; v < DEC_NV; ++v) {
+            const int s = s0 + (v * DEC_THREADS + tid) * DEC_V;
+            if (s <= t && s + DEC_V > lo) {                               // (s + DEC_V <= lda: rows are 8-aligned and t < Lcap <= lda)
+                // aligned 16-byte loads; positions below lo and past t inside a vector meet a zero tap (the history holds finite values only)
+                typename Elem<DT>::type raw[DEC_V];
+                __builtin_memcpy(raw, __builtin_assume_aligned(row + (size_t)s * ES, 16), sizeof(raw));
+                float x[DEC_V];
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) x[e] = Elem<DT>::dec(raw[e]);
+                HY_UNROLL
+                for (int e = 0; e < DEC_V; ++e) {
+                    const bool ok = s + e <= t && s + e >= lo;
+                    const float kv = ks[ok ? t - s - e - kb : 0];
+                    const float kk = ok ? kv : 0.f;
+                    acc = __builtin_fmaf(kk, x[e], acc);
+                }
+            }
+        }
+        acc = cm_wave_sum(acc);
+        HY_LDS float* rb = red + 4 * (b & 1);
+        if ((tid & 63) == 0) rb[tid >> 6] = acc;
+        __syncthreads();
+        if (tid == 0) a.part[((size_t)blockIdx.x * a.B + b) * a.D + c] = (rb[0] + rb[1]) + (rb[2] + rb[3]);
+    }
+}
+
+// ONE workgroup: every thread reads t and lo before the barrier, one lane advances the position after
+template <int DT>
+__global__ void __launch_bounds__(DEC_POST_THREADS) decode_post_la_kernel(DecLaArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int t = a.pos[0], lo = a.base[0];
+    const bool valid = dec_la_valid(a, t, lo);
+    if (valid) {
+        const int nl = t / DEC_CHUNK - lo / DEC_CHUNK + 1;                    // live chunks: 1 or 2
+        const elem_t* vg = reinterpret_cast<const elem_t*>(a.vg);
+        elem_t* z = reinterpret_cast<elem_t*>(a.z);
+        for (int i = threadIdx.x; i < a.B * a.D; i += DEC_POST_THREADS) {
+            const int b = i / a.D, d = i % a.D;
+            float y = a.carry[((size_t)b * a.W + (t - lo)) * a.D + d];
+            for (int x = 0; x < nl; ++x) y += a.part[((size_t)x * a.B + b) * a.D + d];
+            const float u = Elem<DT>::dec(vg[((size_t)b * a.D + d) * a.lda + t]);
+            if (a.fb != nullptr) y = __builtin_fmaf(u, a.fb[d], y);
+            const float yr = Elem<DT>::dec(Elem<DT>::cvt(y));                 // the forward's convolution output is stored in the I/O type
+            z[i] = Elem<DT>::cvt(yr * a.x0[i]);                                // cm_post_fwd: y * c0, rounded once
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && valid) a.pos[0] = t + 1;
 }
 
 // ---- token sampling: the last node of the per-token graph (C ABI: hyena_decode_sample) ---------------------------------------------------

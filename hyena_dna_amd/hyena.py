@@ -452,15 +452,18 @@ class HyenaOperator(nn.Module):
         return y, xT, vg
 
     # ---- incremental decoding (hyena_dna_amd/inference.py, csrc/decode_kernels.h) ----------------------------------------------------------------
-    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, **kwargs):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, lookahead=None, **kwargs):
         """A ``HyenaDecodeState`` for up to batch_size sequences of up to max_seqlen positions, to be put into
         ``InferenceParams.key_value_memory_dict`` under this operator's ``layer_idx`` (or the operator itself when it has none).  The cache is a
         snapshot of the weights at this call, as a key-value cache is: build a new one after the weights change.
 
         ``fan = n > 1`` with ``prompt_len``: batch_size = G n rows that continue G prompts of prompt_len positions n times each; the prefill
-        then takes the G prompts, the steps all G n rows, and the history below (prompt_len // 8192) * 8192 is kept once per prompt."""
+        then takes the G prompts, the steps all G n rows, and the history below (prompt_len // 8192) * 8192 is kept once per prompt.
+
+        ``lookahead = W`` (1 ... 64): a step reads a carry taken once per W positions and the columns written since, not the whole history
+        (``HyenaDecodeState``); None / 0: the plain step."""
         from .inference import HyenaDecodeState
-        return HyenaDecodeState(self, batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len)
+        return HyenaDecodeState(self, batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len, lookahead=lookahead)
 
     def _decode_key(self):
         return self.layer_idx if getattr(self, "layer_idx", None) is not None else self
@@ -475,6 +478,10 @@ class HyenaOperator(nn.Module):
         st = ip.key_value_memory_dict.get(self._decode_key())
         if st is None:
             raise ValueError("inference_params holds no decode cache for this operator: fill key_value_memory_dict from allocate_inference_cache")
+        W = getattr(ip, "lookahead", None)                                   # (flash_attn's own object has none: the cache's window holds)
+        if W is not None and int(W) != st.W:
+            raise ValueError(f"inference_params.lookahead = {W}, but this operator's decode cache was built with lookahead = {st.W}: "
+                             "give allocate_inference_cache and InferenceParams the same window")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise ValueError("incremental decoding is inference only: run it under torch.no_grad() / torch.inference_mode(), or freeze the parameters")
         B, l, _ = u.shape

@@ -7,13 +7,15 @@ dot product over the history of the convolution's input ``vg = v * x1``.  ``Hyen
 memory: one captured graph serves every position; one int for the batch, or one per row after a right-padded prefill with
 ``InferenceParams.lengths_per_sample``) and the step's small buffers -- and ``HyenaOperator.forward(u, inference_params=ip)``
 fills it with a prefill (``ip.seqlen_offset == 0``) and advances it afterwards by one position per call, or by the T known positions of a
-``(B, T, D)`` input in block steps that stream the history once per 64 positions (``step_block``; csrc/decode_kernels.h).
+``(B, T, D)`` input in block steps that stream the history once per 64 positions (``step_block``; csrc/decode_kernels.h).  With
+``lookahead=W`` a cache takes the history's share of the next W outputs ahead, once per W positions, and a step reads that carry and the
+columns written since, not the whole history.
 """
 import torch
 
 from . import _lib
 
-__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable"]
+__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable", "check_lookahead"]
 
 
 class InferenceParams:
@@ -26,10 +28,14 @@ class InferenceParams:
     ``allow_append`` (this package's addition; an attribute set on flash_attn's own object serves as well): with it a call at
     ``seqlen_offset > 0`` with SEVERAL positions per sequence appends them all to the cache in block steps
     (``HyenaDecodeState.step_block``).  Without it such a call stays the error it has always been: a decode loop that hands the model more
-    than its one new token by mistake must not move the cache."""
+    than its one new token by mistake must not move the cache.
+
+    ``lookahead`` (this package's addition): the window W the caches of ``key_value_memory_dict`` were (or are to be) built with
+    (``allocate_inference_cache(..., lookahead=W)``; None / 0: none).  Every ``HyenaDecodeState`` keeps its own, which is the one that acts;
+    the cached forward of every operator refuses (``ValueError``) a cache whose window is not this one, so the two cannot disagree."""
 
     def __init__(self, max_seqlen, max_batch_size, seqlen_offset=0, batch_size_offset=0, key_value_memory_dict=None, lengths_per_sample=None,
-                 allow_append=False):
+                 allow_append=False, lookahead=None):
         self.max_seqlen = max_seqlen
         self.max_batch_size = max_batch_size
         self.seqlen_offset = seqlen_offset
@@ -37,6 +43,7 @@ class InferenceParams:
         self.key_value_memory_dict = {} if key_value_memory_dict is None else key_value_memory_dict
         self.lengths_per_sample = lengths_per_sample
         self.allow_append = allow_append
+        self.lookahead = check_lookahead(lookahead)
 
     @property
     def sequence_len_offset(self):
@@ -52,6 +59,14 @@ class InferenceParams:
         self.seqlen_offset = 0
         if self.lengths_per_sample is not None:
             self.lengths_per_sample.zero_()
+
+
+def check_lookahead(lookahead):
+    """None / 0 (no lookahead) or a window of 1 ... 64 positions -> the window as an int (0: none)"""
+    W = 0 if lookahead is None else int(lookahead)
+    if not 0 <= W <= _lib.DECODE_TMAX:
+        raise ValueError(f"lookahead={lookahead}: None / 0, or a window of 1 ... {_lib.DECODE_TMAX} positions")
+    return W
 
 
 def check_decodable(op, max_seqlen=None):
@@ -95,15 +110,28 @@ class HyenaDecodeState:
     prompt g).  The prefill runs over the G prompts; the history below ``S = (prompt_len // 8192) * 8192`` is the same for the n rows of a
     group and is kept once -- ``hist_shared`` (G, D, S) -- and ``hist`` (batch_size, D, max_seqlen - S) holds every row's columns from S
     on.  The step runs the ``_fan`` kernels, whose results equal those of the plain step on the replicated history bit for bit.  A prompt
-    shorter than 8192 positions has S = 0: nothing is shared in the step (which is launch-bound there), the prefill is still paid once."""
+    shorter than 8192 positions has S = 0: nothing is shared in the step (which is launch-bound there), the prefill is still paid once.
 
-    def __init__(self, op, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None):
+    ``lookahead = W`` (1 ... 64; None / 0: none, and then nothing below exists or runs): the step stops streaming the history.  The
+    convolution is linear in it, so a REFRESH at position t0 takes the share of outputs t0 ... t0 + W - 1 that comes from positions below t0
+    in one pass over the history (``carry`` (B, W, D) fp32, ``base`` = t0 in device memory), and a step at t in that window reads
+    ``carry[:, t - base]`` and the columns base ... t only (``decode_conv_la`` / ``decode_post_la``).  The same sum in another order: the
+    results differ from the plain step's by fp32 rounding.  The schedule lives on the host and reads nothing back: a refresh ends
+    ``store_prefill``, and ``step`` runs one first whenever the window is used up (``la_used == W``).  A caller that replays captured steps
+    (``GraphedDecodeStep``) sets ``la_external`` -- ``step`` then neither refreshes nor counts -- and calls ``la_before_step()`` before
+    every replay.  Not with ``fan > 1``, ragged prompts or block steps (follow-ups)."""
+
+    def __init__(self, op, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, lookahead=None):
         check_decodable(op, max_seqlen)
         if int(batch_size) < 1:
             raise ValueError(f"batch_size={batch_size}: at least one sequence")
         self.fan = int(fan)
         if self.fan < 1:
             raise ValueError(f"fan={fan}: at least one continuation per prompt")
+        self.W = check_lookahead(lookahead)
+        if self.W and self.fan > 1:
+            raise NotImplementedError("a decode cache with lookahead and fan > 1 (num_return_sequences > 1) is out of scope: the carry serves "
+                                      "the plain cache only")
         self.S = 0
         if self.fan > 1:
             if int(batch_size) % self.fan != 0:
@@ -141,6 +169,26 @@ class HyenaDecodeState:
         self.z = torch.empty(self.B, D, dtype=self.dtype, device=dev)
         self.part = _lib.decode_partials(self.B, D, L, dev)
         self.block_buf = None                                                         # step_block's part / x0 / z: allocated on first use
+        # lookahead: allocated only when asked for
+        self.carry = self.carry_part = self.la_part = self.base = None
+        self.la_used, self.la_external, self.la_rows = 0, False, self.B
+        if self.W:
+            self.carry = torch.zeros(self.B, self.W, D, dtype=torch.float32, device=dev)
+            self.carry_part = _lib.decode_carry_partials(self.B, D, L, self.W, dev)
+            self.la_part = torch.empty(2, self.B, D, dtype=torch.float32, device=dev)
+            self.base = torch.zeros(1, dtype=torch.int32, device=dev)                 # (position 0 with a zero carry is a valid window)
+
+    def refresh(self):
+        """the carry of the W outputs from the current position on, in one pass over the history (the rows of the last prefill); then
+        ``base`` = that position"""
+        _lib.decode_carry(self.k, self.hist, self.carry_part, self.carry, self.pos, self.base, self.la_rows, self.L)
+        self.la_used = 0
+
+    def la_before_step(self):
+        """the host's side of one lookahead step: a refresh first if the window is used up, then one more position counted"""
+        if self.la_used >= self.W:
+            self.refresh()
+        self.la_used += 1
 
     def store_prefill(self, xT, vg, P, lengths=None):
         """after the prefill forward over P positions: its convolution input vg (B, D, P) and the last two in_proj outputs of xT (3D, B, P).
@@ -149,6 +197,9 @@ class HyenaDecodeState:
         The model is causal, so everything below lengths[b] is what the unpadded prompt gives; the cache then keeps one position per row
         (``pos_rows``) and ``step`` runs the per-row kernels.  Device work only: nothing here reads ``lengths`` on the host."""
         B = vg.shape[0]
+        if self.W and lengths is not None:
+            raise NotImplementedError("a decode cache with lookahead keeps one position for the batch: ragged prompts (lengths) with lookahead "
+                                      "are out of scope")
         if self.fan > 1:
             if lengths is not None:
                 raise NotImplementedError("a decode cache with fan > 1 holds prompts of one length: ragged prompts with fan-out are out of scope")
@@ -173,6 +224,9 @@ class HyenaDecodeState:
             self.tail[:, :B].zero_()
             self.tail[:, :B, 2 - n:].copy_(xT[:, :, P - n:P])
             self.pos.fill_(P)
+            if self.W:
+                self.la_rows = B
+                self.refresh()
             return
         if lengths.shape != (B,) or lengths.dtype != torch.int32 or lengths.device != self.hist.device:
             raise ValueError(f"lengths must be a ({B},) int32 tensor on {self.hist.device} (got {tuple(lengths.shape)} {lengths.dtype} on {lengths.device})")
@@ -204,6 +258,15 @@ class HyenaDecodeState:
             _lib.decode_conv_rows(self.k, self.hist, self.part, self.pos_rows, B, self.L)
             _lib.decode_post_rows(self.part, self.hist, self.fb, self.x0, z, self.pos_rows, B, self.L)
             return z
+        if self.W:
+            if B > self.la_rows:
+                raise ValueError(f"a lookahead step takes at most the {self.la_rows} rows of the prefill (got {B}): the carry covers those")
+            if not self.la_external:
+                self.la_before_step()
+            _lib.decode_pre(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L)
+            _lib.decode_conv_la(self.k, self.hist, self.la_part, self.pos, self.base, B, self.W, self.L)
+            _lib.decode_post_la(self.la_part, self.carry, self.hist, self.fb, self.x0, z, self.pos, self.base, B, self.L)
+            return z
         _lib.decode_pre(x2, self.bin, self.w, self.b, self.tail, self.hist, self.x0, self.pos, self.L)
         _lib.decode_conv(self.k, self.hist, self.part, self.pos, B, self.L)
         _lib.decode_post(self.part, self.hist, self.fb, self.x0, z, self.pos, B, self.L)
@@ -226,6 +289,9 @@ class HyenaDecodeState:
         calls of ``step`` bit for bit.  ``z`` is a view of the cache's scratch: the next block step overwrites it."""
         if self.ragged:
             raise NotImplementedError("a decode cache in ragged mode (prefill with lengths) has no block step: one position per row and call")
+        if self.W:
+            raise NotImplementedError("a decode cache with lookahead has no block step (allow_append): appending known positions inside a "
+                                      "window is out of scope")
         B, T, _ = x3.shape
         if not 1 <= T <= _lib.DECODE_TMAX:
             raise ValueError(f"a block step takes 1 ... {_lib.DECODE_TMAX} positions (got {T})")

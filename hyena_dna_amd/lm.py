@@ -368,7 +368,7 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
                  cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
-                 stop_check_every=0, num_return_sequences=1, **kwargs):
+                 stop_check_every=0, num_return_sequences=1, lookahead=None, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
@@ -392,9 +392,23 @@ class GenerationMixin:
         a step streams below that point grow with n.  The step's results are those of ``generate(input_ids.repeat_interleave(n, 0))`` bit
         for bit.  Under the device sampler the rows of a group differ because the draw depends on the row index (under ``"torch"``
         through the global generator); greedy rows are all equal.  A prompt shorter than 8192 positions shares nothing in the step, which
-        is launch-bound there -- it still saves the prefill.  Not together with ``lengths``."""
+        is launch-bound there -- it still saves the prefill.  Not together with ``lengths``.
+
+        ``lookahead=W`` (1 ... 64; None / 0: off, today's step launch for launch): every layer's cache takes the history's share of the
+        next W outputs ahead, one pass over the history per W tokens, and a step reads that carry and the columns written since, not the
+        whole prompt (``HyenaDecodeState``).  The same sums in another order: logits differ from the plain cached step's by fp32 rounding.
+        Needs ``use_cache=True``; works with both samplers, ``stop_check_every`` and ``cg=True`` (one replay per token, plus one group of
+        refresh launches every W tokens).  Not with ``lengths`` or ``num_return_sequences > 1`` (out of scope, follow-ups)."""
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
+        from .inference import check_lookahead
+        W = check_lookahead(lookahead)
+        if W and not use_cache:
+            raise ValueError("generate(lookahead=W) carries the history's share of the cached step: it needs use_cache=True")
+        if W and lengths is not None:
+            raise NotImplementedError("generate(lookahead=W, lengths=...): lookahead for ragged prompts is out of scope (one position per batch)")
+        if W and int(num_return_sequences) > 1:
+            raise NotImplementedError("generate(lookahead=W, num_return_sequences > 1): lookahead for fan-out caches is out of scope")
         n = int(num_return_sequences)
         if n < 1:
             raise ValueError(f"num_return_sequences={num_return_sequences}: at least one continuation per prompt")
@@ -412,7 +426,7 @@ class GenerationMixin:
         if sampler == "device":
             return self._generate_device(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
                                          use_cache, cg, 1.0 if top_p is None else float(top_p), eos_token_id, seed, vocab_size,
-                                         int(stop_check_every), fan=n)
+                                         int(stop_check_every), fan=n, lookahead=W)
         if wants_device or stop_check_every:
             raise ValueError(f"sampler='torch' does not serve {', '.join(wants_device + ['stop_check_every'] * bool(stop_check_every))}: "
                              "use sampler='device'")
@@ -428,8 +442,9 @@ class GenerationMixin:
         elif ids.shape[1] < max_length:
             from .inference import InferenceParams
             B = ids.shape[0] * n
-            ip = InferenceParams(max_seqlen=max_length, max_batch_size=B)
-            ip.key_value_memory_dict = self.allocate_inference_cache(B, max_length, **({} if n == 1 else dict(fan=n, prompt_len=ids.shape[1])))
+            ip = InferenceParams(max_seqlen=max_length, max_batch_size=B, lookahead=W)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, max_length, **({} if n == 1 else dict(fan=n, prompt_len=ids.shape[1])),
+                                                                     **(dict(lookahead=W) if W else {}))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
             last = _last_logits(self(ids, inference_params=ip))
@@ -457,7 +472,7 @@ class GenerationMixin:
 
 
     def _generate_device(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
-                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1):
+                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1, lookahead=0):
         """generate() with the device sampler: the prefill, one eager sampler call on its last logits (row b's own last position for ragged
         prompts), then N - 1 steps that each end with the sampler kernel writing the next step's input ids in place -- with ``cg`` N - 1
         graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front.  ``fan = n > 1``:
@@ -500,8 +515,9 @@ class GenerationMixin:
             col = torch.full((B,), P, dtype=torch.int32, device=dev)
         smp, n_done = None, 0
         if N > 0:
-            ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths)
-            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N, **({} if fan == 1 else dict(fan=fan, prompt_len=P)))
+            ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths, lookahead=lookahead)
+            ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N, **({} if fan == 1 else dict(fan=fan, prompt_len=P)),
+                                                                     **(dict(lookahead=lookahead) if lookahead else {}))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
             out = self(input_ids, inference_params=ip)
@@ -871,11 +887,13 @@ class HyenaDNALM(nn.Module, GenerationMixin):
     def _mixers(self):
         return [getattr(blk.mixer, "layer", blk.mixer) for blk in self.backbone.layers]      # (a CheckpointedModule is unwrapped)
 
-    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, **kwargs):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, fan=1, prompt_len=None, lookahead=None, **kwargs):
         """{layer key: HyenaDecodeState} for InferenceParams.key_value_memory_dict (flash_attn's generate assigns it that way).  Every layer must
         be servable (HyenaOperator._forward_cached's refusals apply here, up front).  The caches are snapshots of the weights at this call.
-        ``fan`` / ``prompt_len``: batch_size = G fan rows continue G prompts of prompt_len positions (``HyenaOperator.allocate_inference_cache``)."""
-        return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len)
+        ``fan`` / ``prompt_len``: batch_size = G fan rows continue G prompts of prompt_len positions; ``lookahead``: every layer's step reads
+        a carry taken once per W positions, not its whole history (``HyenaOperator.allocate_inference_cache``)."""
+        return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len,
+                                                            lookahead=lookahead)
                 for m in self._mixers()}
 
     def forward(self, input_ids, position_ids=None, inference_params=None, state=None):
@@ -1128,25 +1146,37 @@ class GraphedDecodeStep:
         emb = model.backbone.embeddings
         self.pos_ids = torch.zeros(1, dtype=torch.long, device=dev) if emb.max_position_embeddings > 0 else None
         states = list(inference_params.key_value_memory_dict.values())
-        side = torch.cuda.Stream(dev)
-        self._side = side
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            snap = [(s.tail.clone(), s.pos.clone(), s.pos_rows.clone()) for s in states]
-            restore_sampler = sampler.snapshot(max(1, int(warmup))) if sampler is not None else None
-            for _ in range(max(1, int(warmup))):
-                self._run()
-            for s, (tail, pos, pos_rows) in zip(states, snap):
-                s.tail.copy_(tail)
-                s.pos.copy_(pos)
-                s.pos_rows.copy_(pos_rows)
-            if restore_sampler is not None:
-                restore_sampler()
-            side.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=side):
-                self.logits = self._run()
-        torch.cuda.current_stream(dev).wait_stream(side)
+        # lookahead caches: the graph holds the step only.  From here on their steps neither refresh nor count (a warm-up step past the
+        # window is parked by the kernels; ``base``, the carry and the host counters stay as they are) and every replay is preceded by
+        # ``la_before_step`` on the current stream: the refresh when one is due, and the count.
+        self._la = [s for s in states if getattr(s, "W", 0)]
+        for s in self._la:
+            s.la_external = True
+        try:
+            side = torch.cuda.Stream(dev)
+            self._side = side
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                snap = [(s.tail.clone(), s.pos.clone(), s.pos_rows.clone()) for s in states]
+                restore_sampler = sampler.snapshot(max(1, int(warmup))) if sampler is not None else None
+                for _ in range(max(1, int(warmup))):
+                    self._run()
+                for s, (tail, pos, pos_rows) in zip(states, snap):
+                    s.tail.copy_(tail)
+                    s.pos.copy_(pos)
+                    s.pos_rows.copy_(pos_rows)
+                if restore_sampler is not None:
+                    restore_sampler()
+                side.synchronize()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, stream=side):
+                    self.logits = self._run()
+            torch.cuda.current_stream(dev).wait_stream(side)
+        except BaseException:
+            # no graph came of it: the caches go back to the eager schedule (an eager step() refreshes and counts again)
+            for s in self._la:
+                s.la_external = False
+            raise
 
     def _run(self):
         out = self.model(self.ids, position_ids=self.pos_ids, inference_params=self.ip)
@@ -1160,6 +1190,8 @@ class GraphedDecodeStep:
         self.ids.copy_(input_ids, non_blocking=True)
         if self.pos_ids is not None:
             self.pos_ids.fill_(int(self.ip.seqlen_offset))
+        for s in self._la:
+            s.la_before_step()
         self.graph.replay()
         return self.logits
 
@@ -1167,6 +1199,8 @@ class GraphedDecodeStep:
         """with a sampler: the step for the tokens the previous replay (or an eager sampler call on ``ids``) left in the id buffer"""
         if self.pos_ids is not None:
             self.pos_ids.fill_(int(self.ip.seqlen_offset))
+        for s in self._la:
+            s.la_before_step()
         self.graph.replay()
 
     def release(self):
@@ -1174,6 +1208,8 @@ class GraphedDecodeStep:
             return
         from . import _lib
         dev = self.ids.device
+        for s in self._la:
+            s.la_external = False
         self.graph = None
         self.logits = None
         torch.cuda.synchronize(dev)

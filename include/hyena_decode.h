@@ -56,7 +56,28 @@
  * its summation order (csrc/decode_kernels.h).  The history columns up to t0 + T - 1 + 7 must hold finite values (they are read for the
  * block's earlier outputs against a zero tap).  If t0 < 0 (fan: t0 < S) or t0 + T > Lcap the kernels do nothing and the position stays.
  * Bad arguments -- T outside [1, HYENA_DECODE_TMAX] and everything the single-position and fan entry points refuse -- return
- * HYENA_ERR_BAD_ARG before anything is launched.  There is no block form of the per-row (_rows) step. */
+ * HYENA_ERR_BAD_ARG before anything is launched.  There is no block form of the per-row (_rows) step.
+ *
+ * Lookahead carry (hyena_decode_carry, hyena_decode_conv_la, hyena_decode_post_la; the plain cache only): the convolution is linear in the
+ * history, so the share of the next W outputs that comes from the positions already cached is taken ahead, in ONE pass over the history,
+ * and a step then reads only the columns written since.  1 <= W <= HYENA_DECODE_TMAX.
+ *   carry : (B, W, D) fp32, element (b, j, d) at (b W + j) D + d;  base : one int in device memory, the position of the last refresh
+ * hyena_decode_carry, with t0 = *pos: carry[b, j, d] = sum_{s < t0} k[d, t0 + j - s] vg[b, d, s] for 0 <= j < min(W, Lcap - t0) (the other
+ * slots are not written), then *base = t0 (a one-thread launch behind the others).  `part` is hyena_decode_carry_partial_floats(B, D, Lcap,
+ * W) fp32 of scratch, [chunk][B][W][D], written for the chunks that start below t0 and summed in chunk order; no atomics.  History columns
+ * at and past t0 contribute exactly nothing whatever they hold (up to 7 of them are loaded); t0 = 0 gives exact zeros and reads no
+ * history.  t0 outside [0, Lcap): nothing is written, *base stays.
+ * hyena_decode_conv_la / hyena_decode_post_la are hyena_decode_conv / hyena_decode_post for a position t = *pos with lo = *base <= t < lo + W
+ * (between them hyena_decode_pre is used as it is): conv_la sums over s in [lo, t] only -- part is 2 B D fp32, [x][B][D] for chunk
+ * lo / 8192 + x, x = 1 written only if t has reached that chunk -- and post_la adds carry[b, t - lo, d], then the one or two partials in
+ * chunk order, then does what hyena_decode_post does (fb, the rounding, the gate, *pos = t + 1).  Columns below lo inside the first loaded
+ * vector and up to 7 past t meet a zero tap and must be finite.  With lo = 0 and a zero carry the results equal those of
+ * hyena_decode_conv + hyena_decode_post bit for bit.  If t is outside [0, Lcap), lo is negative or t - lo is outside [0, W) both calls
+ * write nothing and the position stays.  hyena_decode_pre knows nothing of the window and parks on t outside [0, Lcap) alone: issued at a
+ * t in the cache but outside [lo, lo + W) it still writes history column t, shifts the tail and writes x0, while conv_la / post_la park
+ * and *pos stays -- so the CALLER keeps lo <= t < lo + W (a hyena_decode_carry before the step whenever t = lo + W) or, where it issues
+ * such a step knowingly (a graph warm-up), saves and restores the tail; column t is rewritten by the real step at t.  Bad arguments -- W outside [1, HYENA_DECODE_TMAX], a null carry or base, and everything the
+ * single-position entry points refuse -- return HYENA_ERR_BAD_ARG before anything is launched. */
 #ifndef HYENA_DECODE_H
 #define HYENA_DECODE_H
 #include <stddef.h>
@@ -106,6 +127,15 @@ int hyena_decode_conv_block_fan(const float* k, int ldk, const void* vgs, const 
                                 int Lcap, int S, int lds, int ldr, int T, int dtype, void* stream);
 int hyena_decode_post_block_fan(const float* part, const void* vgr, const float* fb, const float* x0, void* z, int* pos, int B, int fan, int D,
                                 int Lcap, int S, int ldr, int T, int dtype, void* stream);
+
+/* the lookahead carry (see the header comment): carry (B, W, D) fp32, base one device int; part of conv_la / post_la is 2 B D fp32 */
+size_t hyena_decode_carry_partial_floats(int B, int D, int Lcap, int W);
+int hyena_decode_carry(const float* k, int ldk, const void* vg, float* part, float* carry, const int* pos, int* base, int B, int D, int Lcap,
+                       int lda, int W, int dtype, void* stream);
+int hyena_decode_conv_la(const float* k, int ldk, const void* vg, float* part, const int* pos, const int* base, int B, int D, int Lcap, int lda,
+                         int W, int dtype, void* stream);
+int hyena_decode_post_la(const float* part, const float* carry, const void* vg, const float* fb, const float* x0, void* z, int* pos,
+                         const int* base, int B, int D, int Lcap, int lda, int W, int dtype, void* stream);
 
 /* Token sampling, the last node of the per-token graph: one wavefront per row of `logits` (B, V) `dtype`, row b at b ldl, 1 <= Vlive <= V <= 64
  * (columns >= Vlive, the padded vocabulary, are never chosen).  Row b stands at column c = col[b] of `seq` (B, ncols) int64, row b at b lds:
