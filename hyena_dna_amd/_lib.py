@@ -623,6 +623,38 @@ def bwd_needs_input(spectra, L):
     return spectra is None or not spectra_hold_input(L)
 
 
+# ---- the 32-bit offset limits of the workspace-free plan (L <= 32768) that shapes of this package reach (profiles/limits_local.md) ------------
+# Both are known from the shape alone, so neither may surface as a refusal of the library in the middle of a step.
+def _onchip_r(L):
+    """R = M / 1024 of the workspace-free plan, 0 on the two-level plan"""
+    return lib().hyena_fftconv_fft_size(int(L)) // 1024 if lib().hyena_fftconv_plan(int(L)) == PLAN_ONCHIP else 0
+
+
+def fftconv_check_channels(D, L):
+    """The on-chip kernels address the filter spectrum H [D][M] through one buffer descriptor with 32-bit byte offsets: D M 8 < 2^32.  Raises --
+    before anything is allocated -- where the library would refuse."""
+    if D * 1024 * 8 < 2 ** 32 // 32:               # below the limit at every M <= 32768: the common case asks the library nothing
+        return
+    R = _onchip_r(L)
+    if R and D * 1024 * R * 8 >= 2 ** 32:
+        raise HyenaLibraryError(f"hyena fftconv: {D} channels at L = {L} put the filter spectrum (D x {1024 * R} x 8 bytes) past the 2^32-byte reach "
+                                f"of the on-chip kernels' buffer offsets (L <= 32768): at most {(2 ** 32 - 1) // (1024 * R * 8)} channels per call")
+
+
+def fftconv_bwd_batch(B, D, L, ldx, es):
+    """Batch items one backward call may take.  At L <= 1024 (M = 1024: 32-thread row groups, two to a wavefront) the backward kernels address
+    dout / u / du through ONE descriptor over the whole tensor with 32-bit byte offsets, B D ldx es < 2^32, and the library refuses anything
+    larger (B = 8192 at D = 256, L = 1024, 16-bit).  fftconv_bwd cuts such a batch into slices of this many items -- du is per item; dk and dbias
+    are sums over the batch, added slice by slice."""
+    if B * D * ldx * es < 2 ** 32 or _onchip_r(L) != 1:
+        return B
+    nb = (2 ** 32 - 1) // (D * ldx * es)
+    if nb < 1:
+        raise HyenaLibraryError(f"hyena fftconv backward: one batch item of {D} channels at row pitch {ldx} ({D * ldx * es} bytes) is past the "
+                                f"2^32-byte reach of the 32-bit row offsets at L <= 1024 (L = {L})")
+    return nb
+
+
 def fftconv_fwd(u, k, bias, chunk=None, save=False, grad=None):
     """u (B, D, L), k (D, L) fp32, bias (D,) fp32 or None -> out like u.  u and k may be packed or pitched rows (ld_of); out gets u's pitch.
     save=True additionally returns the saved-spectrum buffer for fftconv_bwd(..., saved=).
@@ -630,6 +662,7 @@ def fftconv_fwd(u, k, bias, chunk=None, save=False, grad=None):
     for it right away instead of being outgrown at the first backward."""
     _require_gpu(u, "u")
     B, D, L = u.shape
+    fftconv_check_channels(D, L)
     u, k = as_rows(u), as_rows(k)
     ldx, ldk = ld_of(u), ld_of(k)
     out = empty_like_rows(u)
@@ -667,8 +700,10 @@ def fftconv_bwd(dout, u, k, bias, need_du=True, need_dk=True, chunk=None, saved=
     the saved buffer holds the filter spectrum alone)."""
     _require_gpu(dout, "dout")
     B, D, L = dout.shape
+    fftconv_check_channels(D, L)
     dout = as_rows(dout)
     ldx = ld_of(dout)
+    nb = fftconv_bwd_batch(B, D, L, ldx, dout.element_size()) if B else 0
     if u is not None:
         u = _same_pitch(as_rows(u), ldx)
     if k is not None:
@@ -681,15 +716,31 @@ def fftconv_bwd(dout, u, k, bias, need_du=True, need_dk=True, chunk=None, saved=
         return du, None if dk is None else dk.zero_(), None if dbias is None else dbias.zero_()
     chunk = _chunk_override() if chunk is None else int(chunk)
     tables = tables_for(dout.device, L)
-    nbytes = lib().hyena_fftconv_workspace_bytes(B, D, L, 1, chunk)
+    # (a sliced batch: the workspace of its slices -- nb items, and the shorter last one, whose dk may be cut into another number of partial rows)
+    nbytes = max(lib().hyena_fftconv_workspace_bytes(b, D, L, 1, chunk) for b in ({B} if nb >= B else {nb, B % nb or nb}))
     ws, stream = workspace_for(dout.device, nbytes)
     bp = bias.data_ptr() if bias is not None else None
     ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     with _backend.guard(dout.device):
         # (with the forward's spectra the library reads neither k nor -- for L > 32768 -- u; k is passed only without them)
-        check(lib().hyena_fftconv_bwd_ld(dout.data_ptr(), ptr(u), None if saved is not None else ptr(k), bp, ptr(du), ptr(dk), ptr(dbias),
-                                         B, D, L, ldx, ldk, dtype_code(dout.dtype), tables.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         chunk, ptr(saved), saved.numel() if saved is not None else 0, stream))
+        if nb >= B:
+            check(lib().hyena_fftconv_bwd_ld(dout.data_ptr(), ptr(u), None if saved is not None else ptr(k), bp, ptr(du), ptr(dk), ptr(dbias),
+                                             B, D, L, ldx, ldk, dtype_code(dout.dtype), tables.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             chunk, ptr(saved), saved.numel() if saved is not None else 0, stream))
+            return du, dk, dbias
+        # the batch in slices that stay inside the kernels' 32-bit row offsets (fftconv_bwd_batch): the saved buffer of this plan holds the filter
+        # spectrum alone, which every slice shares; dk and dbias of the later slices are added to the first one's, in slice order
+        dk_s = empty_like_rows(dk) if need_dk else None
+        db_s = torch.empty_like(dbias) if need_dk else None
+        for b0 in range(0, B, nb):
+            b1, first = min(b0 + nb, B), b0 == 0
+            check(lib().hyena_fftconv_bwd_ld(dout[b0:b1].data_ptr(), ptr(None if u is None else u[b0:b1]), None if saved is not None else ptr(k), bp,
+                                             ptr(None if du is None else du[b0:b1]), ptr(dk if first else dk_s), ptr(dbias if first else db_s),
+                                             b1 - b0, D, L, ldx, ldk, dtype_code(dout.dtype), tables.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             chunk, ptr(saved), saved.numel() if saved is not None else 0, stream))
+            if need_dk and not first:
+                dk += dk_s
+                dbias += db_s
     return du, dk, dbias
 
 

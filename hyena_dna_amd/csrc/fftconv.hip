@@ -385,6 +385,8 @@ static int fwd_impl(const void* u, const float* k, const float* bias, void* out,
         if (saved != nullptr && saved_bytes < oc::spectrum_bytes(D, p.R)) return HYENA_ERR_WORKSPACE;
         if (oc::small_ok(p.R, B, D, L, ld, dtype))          // one launch: the filter transform rides in the convolution kernel
             return oc::launch_small_fwd(p.R, u, out, k, bias, saved, d_tables, B, D, L, ld, dtype, stream);
+        // 32-bit two-row windows of spec_kernel (k) and conv_kernel (u, out) at R = 1
+        if (!oc::pair_window_ok(p.R, (size_t)D, L, ldk, 4) || !oc::pair_window_ok(p.R, (size_t)B * D, L, ldx, elem_size(dtype))) return HYENA_ERR_BAD_ARG;
         void* H = saved ? saved : workspace;
         int st = oc::launch_spec(p.R, k, bias, H, d_tables, D, L, ld, stream);
         if (st) return st;
@@ -459,6 +461,9 @@ static int bwd_impl(const void* dout, const void* u, const float* k, const float
             }
             return oc::launch_small_bwd(p.R, dout, u, du, dk, dbias, H, d_tables, B, D, L, ld, dtype, stream);
         }
+        // spec_kernel's 32-bit two-row window over k at R = 1 (conv_kernel's over dout / du is inside the row-offset limit above: B D ldx >= ldx + L
+        // from two rows on)
+        if (du != nullptr && saved == nullptr && !oc::pair_window_ok(p.R, (size_t)D, L, ldk, 4)) return HYENA_ERR_BAD_ARG;
         if (du != nullptr) {
             const void* H = saved;
             if (H == nullptr) {

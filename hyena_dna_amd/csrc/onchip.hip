@@ -146,6 +146,11 @@ bool small_ok(int R, int B, int D, int L, Pitch ld, int dtype) {
     const size_t es = dtype == DT_F32 ? 4 : 2;
     return (size_t)B * D * ld.ldx * es < ((size_t)1 << 32) && (size_t)D * ld.ldk * 4 < ((size_t)1 << 32);       // 32-bit buffer offsets
 }
+// spec_kernel / conv_kernel at T = 32 (R = 1) put TWO consecutive rows into one workgroup's buffer window: (ld + L) es bytes of it, the second
+// row at byte ld es, both 32-bit.  (From R = 2 on a workgroup owns one row: L es bytes behind a 64-bit base, no limit on the pitch.)
+bool pair_window_ok(int R, size_t rows, int L, int ld, size_t es) {
+    return R != 1 || rows < 2 || ((size_t)ld + (size_t)L) * es < ((size_t)1 << 32);
+}
 #define HY_OC_SWITCH(R, call)                 \
     switch (R) {                              \
         case 1: return call(1);               \

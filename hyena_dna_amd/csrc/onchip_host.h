@@ -20,6 +20,9 @@ void build_tables(int R, float* host_c32);
 // device memory for the filter spectrum H [D][M] (the only intermediate of this path)
 size_t spectrum_bytes(int D, int R);
 
+// whether launch_spec / launch_conv can address `rows` rows of L elements of `es` bytes at pitch ld: always from R = 2 on; at R = 1 two rows share a
+// workgroup's 32-bit buffer window, (ld + L) es < 2^32
+bool pair_window_ok(int R, size_t rows, int L, int ld, size_t es);
 // H = (FFT(k) + bias) / M into `H`
 int launch_spec(int R, const float* k, const float* bias, void* H, const void* tab, int D, int L, Pitch ld, void* stream);
 // out = conv(x, H) (conj = 0) or corr(x, H) (conj = 1)

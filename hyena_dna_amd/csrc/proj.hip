@@ -246,6 +246,10 @@ int hyena_inproj_pre_fwd_ld(const void* u, const void* W, const float* bin, cons
     if (u == nullptr || W == nullptr || w == nullptr || b == nullptr || xT == nullptr || vg == nullptr || Lc < 1 || Lc > Lx ||
         ldv < Lc || !hyena_proj_supported(B, Lx, D, dtype) || bsx < Lx || csx < (long)(B - 1) * bsx + Lx || csx >= ((long)1 << 31))
         return HYENA_ERR_BAD_ARG;
+    // generation 1 holds a lane's vg offset -- channel d0 + (lane >> 3) <= D - 9 times ldv, plus its piece 8 (lane & 7) <= 56 -- and the step to the
+    // lane's second channel, 8 ldv, in 32-bit ELEMENTS (inproj_pre_fwd_kernel: voff0); D - 9 >= 8, so the first bounds the second.  Generation 2 forms
+    // both in 64 bits.
+    if (g_inproj_generation != 2 && (size_t)(D - 9) * (size_t)ldv + 56 >= ((size_t)1 << 32)) return HYENA_ERR_BAD_ARG;
     pj::InProjArgs a;
     a.u = u; a.W = W; a.bin = bin; a.w = w; a.b = b; a.xT = xT; a.vg = vg; a.B = B; a.Lx = Lx; a.Lc = Lc; a.D = D; a.csx = csx; a.bsx = bsx; a.ldv = ldv;
     const size_t P = (size_t)B * Lx;

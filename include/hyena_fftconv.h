@@ -153,7 +153,14 @@ int hyena_fftconv_bwd_saved(const void* dout, const void* u, const float* bias, 
  * are these with that default).  hyena_dna_amd/_lib.py allocates the operator's channel-major tensors with ld = L rounded up to 64 elements
  * and hands PyTorch the [..., :L] views.
  * `saved` / `saved_bytes`: the optional spectrum buffer of hyena_fftconv_fwd_save / _bwd_saved, or NULL / 0.  With `saved` the backward does
- * not read k (and, for L > 32768, not u): they may be NULL then. */
+ * not read k (and, for L > 32768, not u): they may be NULL then.
+ * Limits of the pitches (es = bytes per element of u; HYENA_ERR_BAD_ARG past them, before anything is launched; profiles/limits_local.md has the
+ * offsets behind each).  L > 32768, and 1024 < L <= 32768: none -- every row offset is 64-bit.  L <= 1024, where two 32-thread rows share a
+ * wavefront and hence one 32-bit buffer window:
+ *     forward                         (ldx + L) es < 2^32 from two rows (B D >= 2) on, (ldk + L) 4 < 2^32 from two channels on
+ *     backward                        B D ldx es < 2^32;  without `saved`, with du wanted: (ldk + L) 4 < 2^32 from two channels on
+ * (a call the one-launch kernels take -- L <= 2048, B <= 16 resp. 8, B D ldx es < 2^32 and D ldk 4 < 2^32 -- is inside all of these).
+ * L <= 32768 also needs D M 8 < 2^32 (M = hyena_fftconv_fft_size(L)): 32-bit offsets into the filter spectrum. */
 int hyena_fftconv_fwd_ld(const void* u, const float* k, const float* bias, void* out,
                          int B, int D, int L, int ldx, int ldk, int dtype,
                          const void* d_tables, void* workspace, size_t workspace_bytes, int chunk,

@@ -32,7 +32,10 @@ int hyena_inproj_pre_fwd(const void* u, const void* W, const float* bin, const f
 /* ... on STRIDED / PITCHED outputs (round 5; hyena_fftconv.h, hyena_fftconv_fwd_ld, says why; hyena_mixer.h, hyena_cm_*_ld, defines the layouts):
  * xT row (c, b) at element c csx + b bsx (bsx >= Lx, (B - 1) bsx + Lx <= csx < 2^31); vg row (b, d) at (b D + d) ldv (ldv >= Lc).  The kernel
  * walks the flattened positions in 64-position tiles: with csx a multiple of 8 and bsx = Lx every xT store is 16-byte aligned.  The entry
- * point above = the packed strides (csx = B Lx, bsx = Lx, ldv = Lc). */
+ * point above = the packed strides (csx = B Lx, bsx = Lx, ldv = Lc).
+ * Limit of ldv, generation 1 (hyena_proj_kernel_generation): (D - 9) ldv + 56 < 2^32 -- a lane keeps its channel's vg offset in 32-bit ELEMENTS
+ * (ldv <= 36 092 161 at D = 128, 17 388 531 at D = 256; rows of 2^20 positions are 16 times shorter).  HYENA_ERR_BAD_ARG past it, before the launch.
+ * Generation 2 forms the offset in 64 bits and has no such limit. */
 int hyena_inproj_pre_fwd_ld(const void* u, const void* W, const float* bin, const float* w, const float* b, void* xT, void* vg,
                             int B, int Lx, int Lc, int D, long csx, int bsx, int ldv, int dtype, void* stream);
 

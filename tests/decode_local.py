@@ -108,11 +108,17 @@ def _live(form, t, Tn, S, Lcap):
     return t >= S and t + Tn <= Lcap if form.startswith("block") else (S if form == "fan" else 0) <= t < Lcap
 
 
-def _hist_buffer(hr, B, Bcap, ld, last, T, dev):
+def _dense(shape, fill, dtype, dev, pitch):
+    """the default `alloc` of the runners: a packed tensor (pitch = its last dimension)"""
+    assert pitch == shape[-1]
+    return torch.full(shape, fill, dtype=dtype, device=dev)
+
+
+def _hist_buffer(hr, B, Bcap, ld, last, T, dev, alloc=_dense, pitch=None):
     """(Bcap, D, ld): row b holds its operand up to column last[b], SENTINEL in (last, last | 7], NaN beyond; a row with last[b] None (parked:
     nothing of it is read) NaN throughout; rows b >= B SENTINEL"""
     D = hr.shape[1]
-    buf = torch.full((Bcap, D, ld), NAN, dtype=T, device=dev)
+    buf = alloc((Bcap, D, ld), NAN, T, dev, ld if pitch is None else pitch)
     for b in range(B):
         if last[b] is not None:
             buf[b, :, :last[b] + 1] = hr[b, :, :last[b] + 1]
@@ -121,10 +127,13 @@ def _hist_buffer(hr, B, Bcap, ld, last, T, dev):
     return buf
 
 
-def run_conv(_lib, dev, T, form, B, Bcap, D, Lcap, pos, Tn=1, S=0, fan=1, family="flat", seed=0, ldk_extra=4, label=""):
+def run_conv(_lib, dev, T, form, B, Bcap, D, Lcap, pos, Tn=1, S=0, fan=1, family="flat", seed=0, ldk_extra=4, label="", kpitch=None, rpitch=None,
+             alloc=_dense):
     """one call of hyena_decode_conv / _rows / _fan / _block / _block_fan.  pos: the position (rows: one per row).  Every slot of `part` the
     header names within gamma_40 sum|k vg| of its own chunk's fp64 sum, every other slot bitwise the NaN it held (block: the outputs before a
-    chunk that starts inside the block untouched or exactly 0), inputs and pos unchanged.  -> (figures, part)"""
+    chunk that starts inside the block untouched or exactly 0), inputs and pos unchanged.  -> (figures, part)
+    kpitch / rpitch: the caller's own row pitch of k / of the row history, handed to the library instead of the rows' width; alloc(shape, fill, dtype,
+    dev, pitch) then makes a tensor of `shape` whose rows lie `pitch` elements apart (tests/limits_local.py: gigabytes apart, nothing filled between)."""
     assert form in FORMS and B % fan == 0 and (form in ("fan", "block_fan") or (S == 0 and fan == 1)) and (Tn == 1 or form.startswith("block"))
     lib = _lib.lib()
     code, stream = _lib.dtype_code(T), _lib._backend.stream(dev)
@@ -139,13 +148,14 @@ def run_conv(_lib, dev, T, form, B, Bcap, D, Lcap, pos, Tn=1, S=0, fan=1, family
     nfl = lib.hyena_decode_block_partial_floats(B, D, Lcap, Tn) if form.startswith("block") else lib.hyena_decode_partial_floats(B, D, Lcap)
     assert nfl == nch * B * Tn * D
     ldk, lds, ldr = _ceil(Lcap, 4) + ldk_extra, S + 8, _ceil(max(Lcap - S, 1), 8)
-    k = torch.full((D, ldk), NAN, device=dev)
+    kpitch, rpitch = ldk if kpitch is None else kpitch, ldr if rpitch is None else rpitch
+    k = alloc((D, ldk), NAN, torch.float32, dev, kpitch)
     k[:, :kmax + 1] = kv[:, :kmax + 1]
     vgs = None
     if S:
         vgs = torch.full((G, D, lds), NAN, dtype=T, device=dev)
         vgs[:, :, :S] = hs
-    vgr = _hist_buffer(hr, B, Bcap, ldr, [None if t is None else t - S for t in tmax], T, dev)
+    vgr = _hist_buffer(hr, B, Bcap, ldr, [None if t is None else t - S for t in tmax], T, dev, alloc, rpitch)
     part = torch.full((nch, B, Tn, D), NAN, device=dev)
     posb = torch.tensor(tb if form == "rows" else tb[:1], dtype=torch.int32, device=dev)
     ins = [k, vgr, posb] + ([vgs] if S else [])
@@ -154,15 +164,15 @@ def run_conv(_lib, dev, T, form, B, Bcap, D, Lcap, pos, Tn=1, S=0, fan=1, family
     P = lambda x: None if x is None else x.data_ptr()  # noqa: E731
     with _lib._backend.guard(dev):
         if form == "single":
-            st_ = lib.hyena_decode_conv(P(k), ldk, P(vgr), P(part), P(posb), B, D, Lcap, ldr, code, stream)
+            st_ = lib.hyena_decode_conv(P(k), kpitch, P(vgr), P(part), P(posb), B, D, Lcap, rpitch, code, stream)
         elif form == "rows":
-            st_ = lib.hyena_decode_conv_rows(P(k), ldk, P(vgr), P(part), P(posb), B, D, Lcap, ldr, code, stream)
+            st_ = lib.hyena_decode_conv_rows(P(k), kpitch, P(vgr), P(part), P(posb), B, D, Lcap, rpitch, code, stream)
         elif form == "fan":
-            st_ = lib.hyena_decode_conv_fan(P(k), ldk, P(vgs), P(vgr), P(part), P(posb), B, fan, D, Lcap, S, lds, ldr, code, stream)
+            st_ = lib.hyena_decode_conv_fan(P(k), kpitch, P(vgs), P(vgr), P(part), P(posb), B, fan, D, Lcap, S, lds, rpitch, code, stream)
         elif form == "block":
-            st_ = lib.hyena_decode_conv_block(P(k), ldk, P(vgr), P(part), P(posb), B, D, Lcap, ldr, Tn, code, stream)
+            st_ = lib.hyena_decode_conv_block(P(k), kpitch, P(vgr), P(part), P(posb), B, D, Lcap, rpitch, Tn, code, stream)
         else:
-            st_ = lib.hyena_decode_conv_block_fan(P(k), ldk, P(vgs), P(vgr), P(part), P(posb), B, fan, D, Lcap, S, lds, ldr, Tn, code, stream)
+            st_ = lib.hyena_decode_conv_block_fan(P(k), kpitch, P(vgs), P(vgr), P(part), P(posb), B, fan, D, Lcap, S, lds, rpitch, Tn, code, stream)
         _lib.check(st_)
     assert all(same_bits(a, b) for a, b in zip(ins, keep)), "conv wrote one of its inputs (or pos)"
     # ---- what every slot must hold

@@ -231,9 +231,11 @@ class knobs:
 
 
 # ---- one case ----------------------------------------------------------------------------------------------------------------------------
-def _call(_lib, dev, u, k, bias, dout, need, saved, chunk):
-    """forward (+ the spectra when saved) and backward on the device -> out, du, dk, dbias on the host"""
-    ud, kd, gd = u.to(dev), k.to(dev), dout.to(dev)
+def _call(_lib, dev, u, k, bias, dout, need, saved, chunk, place=None):
+    """forward (+ the spectra when saved) and backward on the device -> out, du, dk, dbias on the host.  place(tensor, "x" | "k"): how u / dout and k
+    reach the device (default: packed); a pitched view makes the wrappers hand its pitch on, and out / du / dk come back at that pitch"""
+    put = place or (lambda t, kind: t.to(dev))
+    ud, kd, gd = put(u, "x"), put(k, "k"), put(dout, "x")
     bd = None if bias is None else bias.to(dev)
     if saved:
         out, sp = _lib.fftconv_fwd(ud, kd, bd, chunk=chunk, save=True)
@@ -243,16 +245,17 @@ def _call(_lib, dev, u, k, bias, dout, need, saved, chunk):
     return tuple(None if t is None else t.cpu() for t in (out, du, dk, db))
 
 
-def run_case(_lib, dev, mp, T, B, D, L, want, need=(1, 1), saved=False, chunk=0, bias=True, env=None, seed=None, label=""):
+def run_case(_lib, dev, mp, T, B, D, L, want, need=(1, 1), saved=False, chunk=0, bias=True, env=None, seed=None, label="", place=None):
     """forward + backward of one shape under one setting of the knobs: the route is `want`, every output within its bound of the fp64
-    reference at every element, types as promised, a second call the same bits.  -> (figures, outputs)"""
+    reference at every element, types as promised, a second call the same bits.  -> (figures, outputs)
+    place: see _call (tests/limits_local.py: the inputs on rows gigabytes apart)."""
     seed = 7 * L + 3 * B + D if seed is None else seed
     u, k, b, dout = inputs(B, D, L, T, seed, bias)
     with knobs(mp, env):
         got_route = route(_lib, B, D, L, bool(need[0]), bool(need[1]), saved, chunk)
         assert got_route == want, ("the case no longer reaches the code it was written for", got_route, want)
-        got = _call(_lib, dev, u, k, b, dout, need, saved, chunk)
-        again = _call(_lib, dev, u, k, b, dout, need, saved, chunk)
+        got = _call(_lib, dev, u, k, b, dout, need, saved, chunk, place)
+        again = _call(_lib, dev, u, k, b, dout, need, saved, chunk, place)
     assert all(same_bits(a, c) for a, c in zip(got, again)), "a second call gives other bits"
     out, du, dk, db = got
     r_out, r_du, r_dk, r_db = ref64(u, k, b, dout)

@@ -289,10 +289,12 @@ def addnorm64(o, Eo, res, lw, lb, eps, K, T):
     return {"residual": (v, Ev), "mean": (m[:, 0], Em[:, 0]), "rstd": (rstd[:, 0], (rstd * rel)[:, 0]), "normed": (y, Ey)}
 
 
-def run_outproj(_lib, dev, T, B, L, Lx, D, gen, xlayout="cm", rows=True, zpacked=False, bias=True, norm=False, seed=0, label="", path=""):
+def run_outproj(_lib, dev, T, B, L, Lx, D, gen, xlayout="cm", rows=True, zpacked=False, bias=True, norm=False, seed=0, label="", path="", lda=None,
+                rowbuf=Buf):
     """hyena_outproj_gate_fwd_ld of generation `gen`: zT against shell_local's post_fwd reference, out at EVERY element against zT_stored W^T + bias,
     bit-equal without the zT side output, bit-equal repeat, the wrapper's bits; norm: hyena_outproj_gate_addnorm_fwd_ld with and without an incoming
-    residual against the fp64 add + LayerNorm of the fp64 product."""
+    residual against the fp64 add + LayerNorm of the fp64 product.  lda / rowbuf: the caller's own row pitch of y, in a buffer of that class
+    (tests/limits_local.py: rows gigabytes apart)."""
     lib, rp = _lib.lib(), _lib.row_pitch
     code, stream = _lib.dtype_code(T), _lib._backend.stream(dev)
     g = torch.Generator().manual_seed(seed)
@@ -302,8 +304,8 @@ def run_outproj(_lib, dev, T, B, L, Lx, D, gen, xlayout="cm", rows=True, zpacked
     w, b, bin_ = w.abs(), 1.0 + b.abs(), None if bin_ is None else bin_.abs()
     x, xs, csx, bsx = _x0(B, Lx, L, D, g, T, dev, xlayout, rp)
     x.view[:D, :, :L] = x.view[:D, :, :L].abs()
-    ys, lda = SL.rows_strides(B, D, L, rows, rp)
-    y = Buf.input(_op((B, D, L), g, T, dev), ys)
+    ys, lda = SL.rows_strides(B, D, L, rows, rp, lda)
+    y = rowbuf.input(_op((B, D, L), g, T, dev), ys)
     W = _op((D, D), g, T, dev, W_SCALE)
     ob = _op((D,), g, T, dev, 0.25).float() if bias else None
     zs, csz, bsz = ((B * L, L, 1), B * L, L) if zpacked else SL.z_strides(D, B, L, False, rp)
@@ -372,7 +374,7 @@ def dgrad_schedule(B, L, D):
     return schedule(B * _ceil(L, NT), 512 // (D // 128), 16)
 
 
-def run_dgrad(_lib, dev, T, B, L, Lx, D, exact, xlayout="cm", rows=True, bias=True, seed=0, label="", path=""):
+def run_dgrad(_lib, dev, T, B, L, Lx, D, exact, xlayout="cm", rows=True, bias=True, seed=0, label="", path="", lda=None, rowbuf=Buf):
     """hyena_outproj_dgrad_gate_bwd_ld: dyc, dxT[0:D] and the five sums of every channel against shell_local's post_bwd expressions at the fp64
     dz^T = W_out^T dy^T, the kernel's rounding of dz^T to T (never stored) inside every bound.  exact: dy in {-1, 1} and three non-zero columns
     of W_out^T in {-1, 1} -- dz^T in {+-1, +-3} is exact in fp32 in any order and in T, its error term vanishes and the bound of every sum stays
@@ -389,8 +391,8 @@ def run_dgrad(_lib, dev, T, B, L, Lx, D, exact, xlayout="cm", rows=True, bias=Tr
     else:
         dy2, Wt = _op((B * L, D), g, T, dev), _op((D, D), g, T, dev, W_SCALE)
     x, xs, csx, bsx = _x0(B, Lx, L, D, g, T, dev, xlayout, rp)
-    ys, lda = SL.rows_strides(B, D, L, rows, rp)
-    y = Buf.input(_op((B, D, L), g, T, dev), ys)
+    ys, lda = SL.rows_strides(B, D, L, rows, rp, lda)                              # (lda / rowbuf: as in run_outproj; y and dyc)
+    y = rowbuf.input(_op((B, D, L), g, T, dev), ys)
     tps = _ceil(L, NT)
     runs, tpw = dgrad_schedule(B, L, D)
     st = _Stats()
@@ -398,7 +400,7 @@ def run_dgrad(_lib, dev, T, B, L, Lx, D, exact, xlayout="cm", rows=True, bias=Tr
     assert lib.hyena_outproj_dgrad_partial_floats(B, L, D) == D * runs * 8, "runs"
     with _lib._backend.guard(dev):
         def call():
-            dyc, dx = Buf((B, D, L), ys, T, dev, SENTINEL), Buf((3 * D, B, Lx), xs, T, dev, SENTINEL)
+            dyc, dx = rowbuf((B, D, L), ys, T, dev, SENTINEL), Buf((3 * D, B, Lx), xs, T, dev, SENTINEL)
             part = Buf((D, runs, 8), (runs * 8, 8, 1), torch.float32, dev, SENTINEL)
             _lib.check(lib.hyena_outproj_dgrad_gate_bwd_ld(dy2.data_ptr(), Wt.data_ptr(), y.flat.data_ptr(), x.flat.data_ptr(), SL._ptr(bin_), w.data_ptr(),
                                                            b.data_ptr(), dyc.flat.data_ptr(), dx.flat.data_ptr(), part.flat.data_ptr(), B, L, Lx, D, csx,
@@ -434,7 +436,8 @@ def run_dgrad(_lib, dev, T, B, L, Lx, D, exact, xlayout="cm", rows=True, bias=Tr
             raise AssertionError(("sums", "worst", dict(channel=i // 5, which=i % 5), float(diff.view(-1)[i]), float(bound.view(-1)[i]), int((diff > bound).sum())))
         st.hold("sums", got, ref, bound)                                              # each channel, each of the five, against its own bound
         st["margin"] = float(bound.max()) / small
-        assert all(torch.equal(p.flat, q.flat) for p, q in zip((dyc, dx, part), again)), "outproj_dgrad_gate_bwd is not repeatable bit for bit"
+        assert all(p.same(q) for p, q in zip((dyc, dx, part), again)), "outproj_dgrad_gate_bwd is not repeatable bit for bit"
+        del again
         dxw = Buf((3 * D, B, Lx), xs, T, dev, SENTINEL)
         dw, pw = _lib.outproj_dgrad_gate_bwd(dy2, Wt, y.view, x.view, bin_, w, b, dxw.view)
         assert torch.equal(dw, dyc.view) and torch.equal(dxw.flat, dx.flat) and torch.equal(pw[:, :, :5], part.view[:, :, :5])

@@ -177,14 +177,24 @@ class Buf:
         torch.as_strided(own, self.shape, self.strides)[index] = True
         return bool((self.flat[~own] == SENTINEL).all())
 
+    def same(self, other):
+        """bit for bit, every element of the storage (tests/limits_local.py's FarBuf: every row and every poisoned band)"""
+        return torch.equal(self.flat, other.flat)
 
-def rows_strides(B, D, L, pitched, row_pitch):
-    ld = row_pitch(L) if pitched else L
+
+def rows_strides(B, D, L, pitched, row_pitch, ld=None):
+    """ld: the caller's own pitch (tests/limits_local.py: rows gigabytes apart)"""
+    if ld is None:
+        ld = row_pitch(L) if pitched else L
     return (D * ld, ld, 1), ld
 
 
-def x_strides(C, B, Lx, layout, row_pitch):
-    """packed / per-sequence pitched / channel rows pitched over the flattened positions -> (strides, csx, bsx)"""
+def x_strides(C, B, Lx, layout, row_pitch, cs=None):
+    """packed / per-sequence pitched / channel rows pitched over the flattened positions -> (strides, csx, bsx); cs: the caller's own channel
+    stride over sequences Lx apart"""
+    if cs is not None:
+        assert cs >= B * Lx
+        return (cs, Lx, 1), cs, Lx
     if layout == "packed":
         cs, bs = B * Lx, Lx
     elif layout == "seq":
@@ -252,20 +262,23 @@ def _hold_elem(st, name, buf, index, ref, E, T):
 
 
 # ---- the channel-major kernels ----------------------------------------------------------------------------------------------------------
-def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False, dzrows=False, bias=True, seed=0, rpw=None, label=""):
+def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False, dzrows=False, bias=True, seed=0, rpw=None, label="", lda=None,
+           csx=None, rowbuf=Buf, xbuf=Buf):
     """cm_pre_fwd, cm_post_fwd, cm_post_bwd, cm_pre_bwd, each on its own on caller-made buffers: every condition of the module docstring, the
-    sentinels, bitwise repeatability of the backward kernels, and the bits of the _lib wrappers on the same layouts.  Returns the figures."""
+    sentinels, bitwise repeatability of the backward kernels, and the bits of the _lib wrappers on the same layouts.  Returns the figures.
+    lda / csx: the caller's own row pitch of the (B, D, L) tensors / channel stride of xT and dxT, in buffers of class rowbuf / xbuf (a Buf that
+    need not fill what lies between its rows: tests/limits_local.py)."""
     lib, rp = _lib.lib(), _lib.row_pitch
     code, stream = _lib.dtype_code(T), _lib._backend.stream(dev)
     g = torch.Generator().manual_seed(seed)
     w, b, bin_ = _params(3 * D, g, dev, bias)
-    xs, csx, bsx = x_strides(3 * D, B, Lx, xlayout, rp)
-    rs, lda = rows_strides(B, D, L, rows, rp)
+    xs, csx, bsx = x_strides(3 * D, B, Lx, xlayout, rp, csx)
+    rs, lda = rows_strides(B, D, L, rows, rp, lda)
     zs, csz, bsz = z_strides(D, B, L, zrows, rp)
     dzs, csdz, bsdz = z_strides(D, B, L, dzrows, rp)
-    x = Buf.input(_operand((3 * D, B, Lx), g, T, dev), xs)
-    y = Buf.input(_operand((B, D, L), g, T, dev), rs)
-    dvg = Buf.input(_operand((B, D, L), g, T, dev), rs)
+    x = xbuf.input(_operand((3 * D, B, Lx), g, T, dev), xs)
+    y = rowbuf.input(_operand((B, D, L), g, T, dev), rs)
+    dvg = rowbuf.input(_operand((B, D, L), g, T, dev), rs)
     dz = Buf.input(_operand((D, B, L), g, T, dev), dzs)
     r = cm_rpw(B, L)
     assert rpw is None or r == rpw
@@ -276,7 +289,8 @@ def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False,
     own_l = (slice(None), slice(None), slice(0, L))
 
     def out(shape, strides, dtype=T):
-        return Buf(shape, strides, dtype, dev, SENTINEL)
+        cls = rowbuf if strides == rs else xbuf if strides == xs else Buf
+        return cls(shape, strides, dtype, dev, SENTINEL)
     with _lib._backend.guard(dev):
         # ---- forward
         vg = out((B, D, L), rs)
@@ -289,6 +303,11 @@ def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False,
                                             csx, bsx, csz, bsz, lda, code, stream))
         ref, E = post_fwd64(x64, bin64, w64, b64, y.view.double(), L)
         _hold_elem(st, "post_fwd", zT, own_l, ref, E, T)
+        # the wrappers of _lib on the same caller-made layouts: the same bits (here, so that vg need not outlive the forward)
+        assert torch.equal(_lib.cm_pre_fwd(x.view, bin_, w, b, L), vg.view)
+        zw = _lib.cm_post_fwd(y.view, x.view, bin_, w, b, rows_out=zrows)
+        assert torch.equal(zw.permute(1, 0, 2) if zrows else zw, zT.view)
+        del vg, zw
 
         # ---- backward, each kernel twice into fresh sentinel-filled buffers
         def post_bwd():
@@ -305,10 +324,12 @@ def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False,
             return dx, part
         dy, dx0, part0 = post_bwd()
         again = post_bwd()
-        assert all(torch.equal(p.flat, q.flat) for p, q in zip((dy, dx0, part0), again)), "cm_post_bwd is not repeatable bit for bit"
+        assert all(p.same(q) for p, q in zip((dy, dx0, part0), again)), "cm_post_bwd is not repeatable bit for bit"
+        del again
         dx1, part1 = pre_bwd()
         again = pre_bwd()
-        assert all(torch.equal(p.flat, q.flat) for p, q in zip((dx1, part1), again)), "cm_pre_bwd is not repeatable bit for bit"
+        assert all(p.same(q) for p, q in zip((dx1, part1), again)), "cm_pre_bwd is not repeatable bit for bit"
+        del again
         R0 = post_bwd64(x64, bin64, w64, b64, y.view.double(), dz.view.double(), L)
         R1 = pre_bwd64(x64, bin64, w64, b64, dvg.view.double(), L)
         _hold_elem(st, "post_bwd.dy", dy, own_l, R0["dy"], R0["E_dy"], T)
@@ -322,9 +343,6 @@ def run_cm(_lib, dev, T, B, L, Lx, D, xlayout="packed", rows=False, zrows=False,
         margin = float(sums_bound(R0["S"], R0["H"], n).max()) / R0["small"]
         st["margin"] = margin
         # ---- the wrappers of _lib on the same caller-made layouts: the same bits
-        assert torch.equal(_lib.cm_pre_fwd(x.view, bin_, w, b, L), vg.view)
-        zw = _lib.cm_post_fwd(y.view, x.view, bin_, w, b, rows_out=zrows)
-        assert torch.equal(zw.permute(1, 0, 2) if zrows else zw, zT.view)
         dxw, partw = out((3 * D, B, Lx), xs), _lib.cm_partials(x.view, L)
         assert tuple(partw.shape) == (3 * D, nrec, CM_NP)
         dyw = _lib.cm_post_bwd(dz.view.permute(1, 0, 2) if dzrows else dz.view, y.view, x.view, bin_, w, b, dxw.view, partw, dz_rows=dzrows)
