@@ -213,6 +213,9 @@ def lib():
         L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
                                           c_void_p, c_void_p, c_void_p]
+        L.hyena_decode_sample_constrained.restype = c_int
+        L.hyena_decode_sample_constrained.argtypes = L.hyena_decode_sample.argtypes[:-1] + [c_void_p, ctypes.c_long, c_int, c_void_p, c_void_p,
+                                                                                           ctypes.c_long, c_void_p]
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -1144,11 +1147,17 @@ def decode_post_la(part, carry, hist, fb, x0, z, pos, base, B, Lcap):
 SAMPLE_MAX_V = 64
 
 
-def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, top_p=1.0, eos=-1, pad=0, vocab=None, scores=None, u_out=None):
+def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, top_p=1.0, eos=-1, pad=0, vocab=None, scores=None, u_out=None,
+                  allow=None, start=None, logprobs=None):
     """logits (B, V <= 64) fp32 / bf16 / fp16, rows contiguous -> row b's token at seq[b, col[b]] and nxt[b]; col advanced, done set on `eos`
     (< 0: none); a parked row (col outside seq's columns) is left alone, a done row only gets nxt[b] = pad.  ``seed``: device int64 (1,);
     ``col`` / ``done``: device int32 (B,); ``seq`` (B, ncols) and ``nxt`` (B,) or (B, 1): int64; ``vocab``: the live columns (default V);
-    ``scores`` (B, ncols, V) fp32 or None receives logits / T at [b, col[b]]; ``u_out`` (B,) fp32 or None the uniform each row drew."""
+    ``scores`` (B, ncols, V) fp32 or None receives logits / T at [b, col[b]]; ``u_out`` (B,) fp32 or None the uniform each row drew.
+
+    ``allow`` / ``start`` / ``logprobs`` all None: hyena_decode_sample.  Otherwise hyena_decode_sample_constrained: ``start`` int32 (B,) the
+    column of every row's first new token; ``allow`` int64 bit masks (N,) -- one row for the batch -- or (B, N), bit v of allow[b, i]: token
+    v may be row b's i-th new token (an empty mask, or i outside [0, N): unconstrained); ``logprobs`` (B, N') fp32 receives at
+    [b, col[b] - start[b]] the emitted token's log-probability under the softmax of the live logits at temperature 1."""
     _require_gpu(logits, "logits")
     assert logits.dim() == 2 and logits.stride(1) == 1
     B, V = logits.shape
@@ -1162,6 +1171,24 @@ def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, t
     assert u_out is None or (u_out.dtype == torch.float32 and u_out.shape == (B,) and u_out.is_contiguous())
     for t in (seed, col, done, seq, nxt, scores, u_out):
         assert t is None or t.device == logits.device
+    if allow is not None or start is not None or logprobs is not None:
+        assert start is not None and start.dtype == torch.int32 and start.shape == (B,) and start.is_contiguous()
+        assert allow is None or (allow.dtype == torch.int64 and allow.dim() in (1, 2) and allow.shape[-1] >= 1 and allow.is_contiguous()
+                                 and (allow.dim() == 1 or allow.shape[0] == B))
+        assert logprobs is None or (logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.shape[0] == B
+                                    and logprobs.shape[1] >= 1 and logprobs.is_contiguous())
+        for t in (allow, start, logprobs):
+            assert t is None or t.device == logits.device
+        with _backend.guard(logits.device):
+            check(lib().hyena_decode_sample_constrained(
+                logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, V, V if vocab is None else int(vocab),
+                float(temperature), int(top_k), float(top_p), seed.data_ptr(), int(eos), int(pad), col.data_ptr(), done.data_ptr(),
+                seq.data_ptr(), seq.stride(0) if B > 1 else ncols, ncols, nxt.data_ptr(), nxt.stride(0) if B > 1 else 1,
+                None if scores is None else scores.data_ptr(), None if u_out is None else u_out.data_ptr(),
+                None if allow is None else allow.data_ptr(), 0 if allow is None or allow.dim() == 1 else allow.shape[1],
+                0 if allow is None else allow.shape[-1], start.data_ptr(), None if logprobs is None else logprobs.data_ptr(),
+                0 if logprobs is None else logprobs.shape[1], _backend.stream(logits.device)))
+        return
     with _backend.guard(logits.device):
         check(lib().hyena_decode_sample(logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, V,
                                         V if vocab is None else int(vocab), float(temperature), int(top_k), float(top_p), seed.data_ptr(),

@@ -409,4 +409,27 @@ int hyena_decode_sample(const void* logits, long ldl, int dtype, int B, int V, i
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
+// ---- constrained token sampling (decode_sample_con_kernel): the same, with an allowed set per new token and the token's log-prob -------------
+int hyena_decode_sample_constrained(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
+                                    const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds,
+                                    int ncols, long long* next, long ldn, float* scores, float* u_out, const unsigned long long* allow,
+                                    long lda, int nallow, const int* start, float* logprobs, long ldp, void* stream) {
+    if (logits == nullptr || seed == nullptr || col == nullptr || done == nullptr || seq == nullptr || next == nullptr || B < 1 || V < 1 ||
+        V > SMP_VMAX || Vlive < 1 || Vlive > V || !(top_p > 0.f && top_p <= 1.f) || !dec_dtype_ok(dtype) || ldl < V || ncols < 1 ||
+        lds < ncols || ldn < 1)
+        return HYENA_ERR_BAD_ARG;
+    if ((allow != nullptr || logprobs != nullptr) && start == nullptr) return HYENA_ERR_BAD_ARG;
+    if (allow != nullptr && (nallow < 1 || (lda != 0 && lda < nallow))) return HYENA_ERR_BAD_ARG;
+    if (logprobs != nullptr && ldp < 1) return HYENA_ERR_BAD_ARG;
+    SampleConArgs a;
+    a.logits = logits; a.scores = scores; a.u_out = u_out; a.seed = seed; a.col = col; a.done = done; a.seq = seq; a.next = next;
+    a.ldl = ldl; a.lds = lds; a.ldn = ldn;
+    a.B = B; a.V = V; a.Vlive = Vlive; a.ncols = ncols; a.top_k = top_k; a.eos = eos; a.pad = pad;
+    a.T = temperature > 1e-6f ? temperature : 1e-6f;
+    a.top_p = top_p;
+    a.allow = allow; a.start = start; a.logprobs = logprobs; a.lda = lda; a.ldp = ldp; a.nallow = allow != nullptr ? nallow : 0;
+    HY_DEC_DISPATCH(decode_sample_con_kernel, dim3(B < SMP_MAX_GRID ? B : SMP_MAX_GRID), SMP_VMAX, SMP_CON_LDS_BYTES);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
 }  // extern "C"

@@ -939,4 +939,164 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_kernel(SampleArgs a) {
     }
 }
 
+// ---- constrained token sampling with token log-probs (C ABI: hyena_decode_sample_constrained) -------------------------------------------------
+// decode_sample_kernel with an allowed set per row and new-token number, and the emitted token's log-probability.  With n = c - start[b] the
+// number of the row's new token, its mask is allow[b lda + n] (lda = 0: one row of masks for the batch) and
+//   A        = { v < Vlive : bit v of the mask }; the whole live vocabulary where allow is null, n lies outside [0, nallow) or no bit below
+//            Vlive is set (the kernel ends a captured graph and cannot raise: it stays total)
+// Every rule above then reads "A" for "the live tokens": ranks are taken among A (a NaN first, then by value, then by index), greedy takes
+// rank 0 of A, k = min(top_k, |A|), the masses are exp((l_i - max_A l) / T) summed in rank order, a row whose rank-0 logit within A is not
+// finite emits that token, and u is the same Philox word of (seed, row, column).  eos ends the row when it is emitted, so only where A holds
+// it.  With A the live vocabulary every value below is the one decode_sample_kernel computes, operation for operation.
+//   logprob  logprobs[b ldp + n] = (l_tok - m) - log(sum_{j < Vlive} exp(l_j - m)), m = max_{j < Vlive} l_j (NaNs skipped by fmaxf): the
+//            model's own distribution at T = 1 over ALL live tokens, in fp32, the sum taken serially in index order by every lane from LDS
+//            (a pure function of the row's logits; lane j computes the term exp(l_j - m), m being taken in the rank loop).  m or the sum
+//            not finite (a live NaN or +inf, or every live logit -inf): NaN.  Written for n in [0, ldp) only.  The terms cross the
+//            second barrier with the ranks and l_tok is read back by rank (ss): the row's path has decode_sample_kernel's barriers and
+//            no more.
+// The mask, start[b] and col[b] are loaded by every lane from one address: every branch around a barrier stays uniform.
+enum { SMP_CON_LDS_BYTES = 5 * SMP_VMAX * 4 };
+// "these values are needed HERE": their loads are issued, together, before this point.  (The empty statement takes its operands in vector
+// registers; the uniform ones go back to scalar registers, so that the branches on them stay scalar branches.)
+#if !defined(HIPEMU)
+#define SMP_UNIFORM_ISSUED3(x, y, z)                                                                                   \
+    do {                                                                                                               \
+        asm volatile("" : "+v"(x), "+v"(y), "+v"(z));                                                                \
+        x = __builtin_amdgcn_readfirstlane(x); y = __builtin_amdgcn_readfirstlane(y); z = __builtin_amdgcn_readfirstlane(z); \
+    } while (0)
+#define SMP_ISSUED2_UNIFORM64(x, m)                                                                                    \
+    do {                                                                                                               \
+        asm volatile("" : "+v"(x), "+v"(m));                                                                         \
+        m = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |                     \
+            (unsigned)__builtin_amdgcn_readfirstlane((int)m);                                                          \
+    } while (0)
+#else
+#define SMP_UNIFORM_ISSUED3(x, y, z) ((void)0)
+#define SMP_ISSUED2_UNIFORM64(x, m) ((void)0)
+#endif
+
+struct SampleConArgs : SampleArgs {
+    const unsigned long long* allow;  // (B or 1, nallow) bit masks, row b at b lda, or null
+    const int* start;                 // (B,) the column of row b's first new token
+    float* logprobs;                  // (B, ldp) fp32 or null
+    long lda, ldp;
+    int nallow;
+};
+
+template <int DT>
+__global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    HY_SMEM(smem);
+    HY_LDS float* sl = HY_LDS_CAST(float, smem);                 // [64] live logits by index
+    HY_LDS float* ss = sl + SMP_VMAX;                            // [64] allowed logits by rank
+    HY_LDS float* sp = ss + SMP_VMAX;                            // [64] masses by rank
+    HY_LDS int* si = HY_LDS_CAST(int, smem) + 3 * SMP_VMAX;      // [64] token by rank
+    HY_LDS float* se = sl + 4 * SMP_VMAX;                        // [64] exp(l - max l) of the live tokens by index (log-prob)
+    const int i = threadIdx.x;
+    const float ninf = -__builtin_inff();
+    const unsigned long long all = a.Vlive >= 64 ? ~0ull : (1ull << a.Vlive) - 1ull;
+    // (every branch around a barrier is taken on col[b] / done[b] / top_k: uniform across the wavefront)
+    // The loads are dependent round trips to memory, and they are what this kernel's time is made of.  Left alone the compiler sinks every
+    // load behind the branch that guards its use -- five trips in a row.  Here col, done and start (of every row, parked or not) go out
+    // together, then the row's logits and its mask together, each group from straight-line code and pinned by SMP_*ISSUED*: two trips.
+    // (Lanes from V on read logit 0 and drop it; a row without a mask reads the seed's word and drops it: valid addresses, no branch.)
+    const unsigned long long seed = a.top_k > 1 ? a.seed[0] : 0ull;
+    const int* first_col = a.start != nullptr ? a.start : a.col;            // (no start: n = 0 -- no mask and no log-prob, the launcher sees to it)
+    for (long b = blockIdx.x; b < a.B; b += gridDim.x) {
+        int c = a.col[b];
+        int fin = a.done[b];
+        int c0 = first_col[b];
+        SMP_UNIFORM_ISSUED3(c, fin, c0);
+        if (c < 0 || c >= a.ncols) continue;                     // parked
+        if (fin != 0) {
+            if (i == 0) a.next[(size_t)b * a.ldn] = a.pad;
+            continue;
+        }
+        const long n = (long)c - c0;
+        const bool masked = a.allow != nullptr && n >= 0 && n < a.nallow;
+        const unsigned long long* mp = masked ? a.allow + ((size_t)b * a.lda + n) : a.seed;
+        float l = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.logits)[(size_t)b * a.ldl + (i < a.V ? i : 0)]);
+        unsigned long long m = mp[0];
+        SMP_ISSUED2_UNIFORM64(l, m);
+        if (!masked) m = 0ull;
+        if (i < a.V) {
+            if (a.scores != nullptr) a.scores[((size_t)b * a.ncols + c) * a.V + i] = l / a.T;
+        } else {
+            l = ninf;
+        }
+        const unsigned long long A = (m & all) != 0ull ? m & all : all;
+        const int nA = __builtin_popcountll(A);
+        const bool live = i < a.Vlive;
+        const bool mine = ((A >> i) & 1ull) != 0ull;             // (A has no bit from Vlive on)
+        sl[i] = live ? l : ninf;
+        __syncthreads();                                         // (also orders the previous row's scan before this row's ss / sp / si)
+        int r = 0;
+        float lmax = ninf;
+        for (int j = 0; j < a.Vlive; ++j) {
+            const float lj = sl[j];
+            // decode_sample_kernel's "j comes before i" without a branch (lj is uniform, and a branch on it costs the loop its unrolling):
+            // a NaN lj fails both of its comparisons, a NaN l both of its own
+            const bool first = ((lj != lj) & ((l == l) | (j < i))) | (lj > l) | ((lj == l) & (j < i));
+            r += (first ? 1 : 0) & (int)((A >> j) & 1ull);
+            lmax = fmaxf(lmax, lj);                              // over ALL live tokens, NaNs skipped
+        }
+        if (mine) {
+            ss[r] = l;
+            si[r] = i;
+        }
+        const bool want_lp = a.logprobs != nullptr && n >= 0 && n < a.ldp;
+        if (want_lp) se[i] = live ? expf(l - lmax) : 0.f;        // by index; read after the barrier below, rewritten after the next row's first
+        __syncthreads();
+        float lsum = 0.f;
+        if (want_lp)
+            for (int j = 0; j < a.Vlive; ++j) lsum += se[j];     // serially in index order, the same sum in every lane
+        int tok;
+        float ltok = ss[0];
+        if (a.top_k <= 1) {
+            tok = si[0];
+        } else {
+            const int k = a.top_k < nA ? a.top_k : nA;
+            if (mine) sp[r] = r < k ? expf((l - ss[0]) / a.T) : 0.f;
+            __syncthreads();
+            float Z = 0.f;
+            for (int q = 0; q < k; ++q) Z += sp[q];
+            const float lim = a.top_p * Z;
+            int nk = 0;
+            float kept = 0.f;                                    // Z': the mass of the nucleus
+            while (nk < k && kept < lim) kept += sp[nk++];
+            unsigned rnd[4];
+            philox4x32_10((unsigned)c, (unsigned)b, (unsigned)seed, (unsigned)(seed >> 32), rnd);
+            const float u = (float)(rnd[0] >> 8) * 5.9604644775390625e-8f;          // 2^-24: exact
+            const float target = u * kept;
+            const float top = ss[0];
+            if (!(top - top == 0.f)) {                           // rank 0 is NaN or +-inf: sp, Z and nk mean nothing
+                tok = si[0];
+            } else {
+                tok = si[nk - 1];
+                ltok = ss[nk - 1];
+                float acc = 0.f;
+                for (int q = 0; q < nk; ++q) {
+                    acc += sp[q];
+                    if (acc > target) {
+                        tok = si[q];
+                        ltok = ss[q];
+                        break;
+                    }
+                }
+            }
+            if (i == 0 && a.u_out != nullptr) a.u_out[b] = u;
+        }
+        if (i == 0) {
+            a.seq[(size_t)b * a.lds + c] = tok;
+            a.next[(size_t)b * a.ldn] = tok;
+            a.col[b] = c + 1;
+            if (tok == a.eos) a.done[b] = 1;
+            if (want_lp) {
+                const bool ok = lmax - lmax == 0.f && lsum - lsum == 0.f;
+                a.logprobs[(size_t)b * a.ldp + n] = ok ? (ltok - lmax) - logf(lsum) : __builtin_nanf("");
+            }
+        }
+    }
+}
+
 }  // namespace hyena

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable", "check_lookahead"]
+__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable", "check_lookahead", "token_mask", "iupac_constraints"]
 
 
 class InferenceParams:
@@ -319,7 +319,12 @@ class DeviceSampler:
     ``seq[b, col[b]]`` and to ``nxt`` (the model's next input ids, (B, 1) int64) and advances ``col`` -- nothing is read on the host, so a
     captured graph may end with the call (``GraphedDecodeStep(..., sampler=...)``)."""
 
-    def __init__(self, seq, col, seed, temperature=1.0, top_k=1, top_p=1.0, eos=None, pad=0, vocab=None, want_scores=False, V=None):
+    def __init__(self, seq, col, seed, temperature=1.0, top_k=1, top_p=1.0, eos=None, pad=0, vocab=None, want_scores=False, V=None, allow=None,
+                 want_logprobs=False, n_new=None):
+        """``allow``: int64 bit masks, (N,) for every row or (B, N): bit v of allow[b, i] lets token v be row b's i-th new token, counted
+        from ``col`` as it stands now (``token_mask``, ``iupac_constraints``).  ``want_logprobs``: ``logprobs`` (B, ``n_new``; default ncols) fp32 receives at
+        [b, i] the log-probability of row b's i-th new token under the softmax of its live logits at temperature 1 (NaN where none was
+        written).  Either one selects hyena_decode_sample_constrained; with neither the sampler runs hyena_decode_sample as before."""
         dev = seq.device
         self.seq, self.col = seq, col
         self.done = torch.zeros_like(col)
@@ -327,20 +332,30 @@ class DeviceSampler:
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
         self.eos, self.pad, self.vocab = (-1 if eos is None else int(eos)), int(pad), vocab
         self.scores = torch.zeros(seq.shape[0], seq.shape[1], V, dtype=torch.float32, device=dev) if want_scores else None
+        self.allow = allow
+        self.start = col.clone() if allow is not None or want_logprobs else None
+        self.logprobs = None
+        if want_logprobs:
+            self.logprobs = torch.full((seq.shape[0], max(int(seq.shape[1] if n_new is None else n_new), 1)), float("nan"), dtype=torch.float32,
+                                       device=dev)
 
     def __call__(self, logits, nxt):
         _lib.decode_sample(logits, self.seed, self.col, self.done, self.seq, nxt, temperature=self.temperature, top_k=self.top_k,
-                           top_p=self.top_p, eos=self.eos, pad=self.pad, vocab=self.vocab, scores=self.scores)
+                           top_p=self.top_p, eos=self.eos, pad=self.pad, vocab=self.vocab, scores=self.scores, allow=self.allow,
+                           start=self.start, logprobs=self.logprobs)
 
     def snapshot(self, steps):
-        """what up to ``steps`` calls from here may change -- col, done, the columns col[b] ... col[b] + steps - 1 of seq (and of scores) --
-        as a function that puts it back (``GraphedDecodeStep``'s warm-up steps run the real kernel)"""
+        """what up to ``steps`` calls from here may change -- col, done, the columns col[b] ... col[b] + steps - 1 of seq (and of scores),
+        the slots col[b] - start[b] ... + steps - 1 of logprobs -- as a function that puts it back (``GraphedDecodeStep``'s warm-up steps
+        run the real kernel)"""
         ncols = self.seq.shape[1]
         col, done = self.col.clone(), self.done.clone()
         idx = (col.to(torch.int64)[:, None] + torch.arange(int(steps), device=col.device)).clamp_(0, ncols - 1)      # (B, steps)
         seq = self.seq.gather(1, idx)
         sidx = None if self.scores is None else idx[:, :, None].expand(-1, -1, self.scores.shape[2])
         scores = None if self.scores is None else self.scores.gather(1, sidx)
+        pidx = None if self.logprobs is None else (idx - self.start.to(torch.int64)[:, None]).clamp_(0, self.logprobs.shape[1] - 1)
+        logprobs = None if self.logprobs is None else self.logprobs.gather(1, pidx)
 
         def restore():
             self.col.copy_(col)
@@ -348,4 +363,41 @@ class DeviceSampler:
             self.seq.scatter_(1, idx, seq)
             if scores is not None:
                 self.scores.scatter_(1, sidx, scores)
+            if logprobs is not None:
+                self.logprobs.scatter_(1, pidx, logprobs)
         return restore
+
+
+# ---- allowed-token masks for the device sampler: pure host code ----------------------------------------------------------------------------
+ALL_TOKENS = -1                                     # every bit set: an unconstrained position
+IUPAC = {"A": "A", "C": "C", "G": "G", "T": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC", "B": "CGT", "D": "AGT",
+         "H": "ACT", "V": "ACG", "N": "ACGT"}
+
+
+def token_mask(ids):
+    """the 64-bit mask with bit v set for every v in ``ids``, as the int an int64 tensor holds (bit 63 makes it negative)"""
+    m = 0
+    for v in ids:
+        v = int(v)
+        if not 0 <= v < _lib.SAMPLE_MAX_V:
+            raise ValueError(f"token id {v}: a mask has one bit per logit column, 0 ... {_lib.SAMPLE_MAX_V - 1}")
+        m |= 1 << v
+    return m - (1 << 64) if m >> 63 else m
+
+
+def iupac_constraints(pattern, token_of=None):
+    """``pattern``: one character per new token, an IUPAC nucleotide code (A C G T, R Y S W K M B D H V N -- N: any of the four bases) or
+    ``.`` for an unconstrained position -> (len(pattern),) int64 masks on the CPU, for ``generate(constraints=...)`` after ``.to(device)``.
+    ``token_of`` maps 'A' 'C' 'G' 'T' to token ids; default: the character tokenizer's (tokenizer.DNACharTokenizerLUT)."""
+    if token_of is None:
+        from .tokenizer import DNACharTokenizerLUT
+        token_of = DNACharTokenizerLUT().vocab
+    out = []
+    for i, ch in enumerate(pattern):
+        if ch == ".":
+            out.append(ALL_TOKENS)
+        elif ch.upper() in IUPAC:
+            out.append(token_mask(token_of[base] for base in IUPAC[ch.upper()]))
+        else:
+            raise ValueError(f"pattern[{i}] = {ch!r}: an IUPAC nucleotide code ({' '.join(IUPAC)}) or '.'")
+    return torch.tensor(out, dtype=torch.int64)

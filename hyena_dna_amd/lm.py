@@ -356,6 +356,54 @@ def _sample(logits, top_k, temperature):
     return logits, nxt
 
 
+def _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G, fan, N, dev):
+    """generate()'s ``allowed_tokens`` / ``constraints`` / ``min_new_tokens`` as the device sampler's masks -> (allow, check): ``allow`` None
+    where none is given, else int64 (N,) or (G fan, N) on ``dev``, their intersection; ``check(V, Vlive)`` raises for an id outside [0, V)
+    and for a position that allows no token below ``Vlive`` (named by row and position).  A wrong shape, dtype or device is refused here.
+    The one read-back -- the highest lowest-set-bit over the masks, and where it stands -- is made HERE, before the prefill is launched
+    (the host then waits for next to nothing); ``check`` compares host numbers once the prefill's logits have told V."""
+    from .inference import token_mask
+    m = int(min_new_tokens)
+    if m < 0:
+        raise ValueError(f"min_new_tokens={min_new_tokens}: a number of tokens")
+    if m and eos_token_id is None:
+        raise ValueError("min_new_tokens keeps eos_token_id out of the first positions: it needs eos_token_id")
+    if allowed_tokens is None and constraints is None and not m:
+        return None, lambda V, Vlive: None
+    ids = None if allowed_tokens is None else [int(v) for v in allowed_tokens]
+    keep = -1 if ids is None else token_mask(v for v in ids if 0 <= v < 64)      # (an id outside: check() names it)
+    if constraints is None:
+        allow = torch.full((N,), keep, dtype=torch.int64, device=dev)
+    else:
+        ok = torch.is_tensor(constraints) and constraints.dtype == torch.int64 and constraints.device == dev
+        if not ok or tuple(constraints.shape) not in ((N,), (G, N)):
+            what = f"{tuple(constraints.shape)} {constraints.dtype} on {constraints.device}" if torch.is_tensor(constraints) else type(constraints).__name__
+            raise ValueError(f"constraints must be a ({N},) or ({G}, {N}) int64 tensor of bit masks on {dev}, N = max_length - the prompt's "
+                             f"columns (got {what})")
+        allow = constraints & keep
+        if allow.dim() == 2 and fan > 1:
+            allow = allow.repeat_interleave(fan, 0)
+    if m and 0 <= int(eos_token_id) < 64:
+        allow = allow.clone()
+        allow[..., :m] &= ~token_mask([eos_token_id])
+    allow = allow.contiguous()
+    flat = allow.reshape(-1)
+    pow2 = torch.ones(64, dtype=torch.int64, device=dev) << torch.arange(64, device=dev)
+    low = torch.where(flat == 0, 64, ((flat & -flat)[:, None] == pow2[None]).int().argmax(1))       # lowest set bit; 64: no bit at all
+    worst, at = torch.stack([low.max(), low.argmax()]).tolist()                                       # the one host read
+
+    def check(V, Vlive):
+        bad = [v for v in ids or () if not 0 <= v < V]
+        if bad:
+            raise ValueError(f"allowed_tokens holds {bad[0]}: the logits have {V} columns")
+        if m and not 0 <= int(eos_token_id) < V:
+            raise ValueError(f"eos_token_id={eos_token_id}: the logits have {V} columns")
+        if worst >= Vlive:
+            where = f"position {at}" if allow.dim() == 1 else f"row {at // N}, position {at % N}"
+            raise ValueError(f"the constraints allow no token below {Vlive} (the live vocabulary) at {where}")
+    return allow, check
+
+
 class GenerationMixin:
     """Greedy / top-k sampling.  Default: by re-running the causal model on the growing prefix (the reference's way: its HyenaOperator
     ignores ``inference_params``).  ``use_cache=True``: one prefill that fills every layer's decode cache, then one incremental step per
@@ -368,7 +416,8 @@ class GenerationMixin:
     @torch.no_grad()
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
                  cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
-                 stop_check_every=0, num_return_sequences=1, lookahead=None, **kwargs):
+                 stop_check_every=0, num_return_sequences=1, lookahead=None, allowed_tokens=None, constraints=None, min_new_tokens=0,
+                 output_logprobs=False, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
@@ -398,7 +447,18 @@ class GenerationMixin:
         next W outputs ahead, one pass over the history per W tokens, and a step reads that carry and the columns written since, not the
         whole prompt (``HyenaDecodeState``).  The same sums in another order: logits differ from the plain cached step's by fp32 rounding.
         Needs ``use_cache=True``; works with both samplers, ``stop_check_every`` and ``cg=True`` (one replay per token, plus one group of
-        refresh launches every W tokens).  Not with ``lengths`` or ``num_return_sequences > 1`` (out of scope, follow-ups)."""
+        refresh launches every W tokens).  Not with ``lengths`` or ``num_return_sequences > 1`` (out of scope, follow-ups).
+
+        Which tokens may come out, and how likely they were (device sampler only; each selects it when ``sampler`` is None).
+        ``allowed_tokens``: a sequence of ids, the only ones any new position may take.  ``constraints``: int64 bit masks on the input's
+        device, (N,) or (B, N) with N = max_length - P -- bit v of constraints[b, i] lets token v be row b's i-th new token, also for
+        ragged prompts (``inference.token_mask``, ``inference.iupac_constraints``); with ``num_return_sequences=n`` a (G, N) tensor holds
+        one row per prompt.  Both given: the intersection.  ``min_new_tokens=m`` takes ``eos_token_id`` out of the first m positions.
+        Ranks, top-k, the nucleus and greedy are taken among the allowed tokens only.  The masks are checked once on entry (one
+        read-back): a position that allows no token below ``vocab_size`` is a ValueError.  ``output_logprobs=True`` adds ``logprobs``
+        (B, number of steps run) fp32 to the returned tuple: the log-probability of every emitted token under the softmax of its live
+        logits at temperature 1 -- the model's own distribution, not the constrained or tempered one -- NaN where the logits hold a NaN
+        or +inf and for the positions of a finished row."""
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
         from .inference import check_lookahead
@@ -418,7 +478,9 @@ class GenerationMixin:
             raise NotImplementedError("generate(num_return_sequences > 1, lengths=...): ragged prompts with fan-out are out of scope "
                                       "(the shared history needs one prompt length)")
         wants_device = [n for n, on in (("top_p", top_p is not None and float(top_p) != 1.0), ("eos_token_id", eos_token_id is not None),
-                                        ("seed", seed is not None), ("vocab_size", vocab_size is not None)) if on]
+                                        ("seed", seed is not None), ("vocab_size", vocab_size is not None),
+                                        ("allowed_tokens", allowed_tokens is not None), ("constraints", constraints is not None),
+                                        ("min_new_tokens", bool(min_new_tokens)), ("output_logprobs", bool(output_logprobs))) if on]
         if sampler is None:
             sampler = "device" if wants_device else "torch"
         if sampler not in ("torch", "device"):
@@ -426,7 +488,8 @@ class GenerationMixin:
         if sampler == "device":
             return self._generate_device(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
                                          use_cache, cg, 1.0 if top_p is None else float(top_p), eos_token_id, seed, vocab_size,
-                                         int(stop_check_every), fan=n, lookahead=W)
+                                         int(stop_check_every), fan=n, lookahead=W, allowed_tokens=allowed_tokens, constraints=constraints,
+                                         min_new_tokens=min_new_tokens, output_logprobs=output_logprobs)
         if wants_device or stop_check_every:
             raise ValueError(f"sampler='torch' does not serve {', '.join(wants_device + ['stop_check_every'] * bool(stop_check_every))}: "
                              "use sampler='device'")
@@ -472,7 +535,8 @@ class GenerationMixin:
 
 
     def _generate_device(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
-                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1, lookahead=0):
+                         use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1, lookahead=0, allowed_tokens=None,
+                         constraints=None, min_new_tokens=0, output_logprobs=False):
         """generate() with the device sampler: the prefill, one eager sampler call on its last logits (row b's own last position for ragged
         prompts), then N - 1 steps that each end with the sampler kernel writing the next step's input ids in place -- with ``cg`` N - 1
         graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front.  ``fan = n > 1``:
@@ -520,6 +584,7 @@ class GenerationMixin:
                                                                      **(dict(lookahead=lookahead) if lookahead else {}))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
+            allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, B // fan, fan, N, dev)
             out = self(input_ids, inference_params=ip)
             logits = out[0] if isinstance(out, tuple) else out
             logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V); fan > 1: (B / fan, P, V)
@@ -535,8 +600,9 @@ class GenerationMixin:
             if seed is None:                           # torch's generator, once per call (greedy draws nothing)
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if top_k > 1 else 0
             seed = torch.tensor([int(seed)], dtype=torch.int64).to(dev)
+            check_masks(V, V if vocab_size is None else int(vocab_size))
             smp = DeviceSampler(seq, col, seed, temperature=temperature, top_k=top_k, top_p=top_p, eos=eos_token_id, pad=pad_token_id,
-                                vocab=vocab_size, want_scores=output_scores, V=V)
+                                vocab=vocab_size, want_scores=output_scores, V=V, allow=allow, want_logprobs=output_logprobs, n_new=N)
             ip.seqlen_offset = P                       # ragged: the furthest any row has got (bounds checks only)
             step = GraphedDecodeStep(self, ip, B, sampler=smp) if cg and N > 1 else None
             nxt = step.ids if step is not None else torch.empty(B, 1, dtype=torch.int64, device=dev)
@@ -566,9 +632,13 @@ class GenerationMixin:
                 scores = tuple(smp.scores.gather(1, idx).unbind(1))
             else:
                 scores = tuple(smp.scores[:, P:P + n_done].contiguous().unbind(1))
+        fields, values = ["sequences", "scores"], [seq, scores]
         if ragged:
-            return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores", "lengths"])(seq, scores, lengths + N)
-        return namedtuple("GreedySearchDecoderOnlyOutput", ["sequences", "scores"])(seq, scores)
+            fields, values = fields + ["lengths"], values + [lengths + N]
+        if output_logprobs:                            # row b's i-th new token at [b, i], ragged or not
+            fields.append("logprobs")
+            values.append(torch.empty(B, 0, device=dev) if smp is None else smp.logprobs[:, :n_done].contiguous())
+        return namedtuple("GreedySearchDecoderOnlyOutput", fields)(*values)
 
 
     def _generate_ragged(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,

@@ -157,6 +157,30 @@ int hyena_decode_sample(const void* logits, long ldl, int dtype, int B, int V, i
                         const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,
                         long long* next, long ldn, float* scores, float* u_out, void* stream);
 
+/* Constrained token sampling with token log-probs: hyena_decode_sample (every argument and rule above) with an allowed set per row and
+ * new-token number.  `start` (B,) int32 is the column of row b's first new token (the prompt length; lengths[b] for ragged prompts), and
+ * n = col[b] - start[b] the number of the token the row draws now.  `allow`: 64-bit masks, row b's mask for its n-th new token at
+ * allow[b lda + n], n < nallow; lda = 0: one row of masks for the whole batch; bit v set: token v may be emitted.  The allowed set is
+ *   A = { v < Vlive : bit v of the mask };  A = the whole live vocabulary where allow is NULL, n lies outside [0, nallow), or the mask has
+ *   no bit below Vlive (the kernel ends a captured graph and cannot raise: it stays a total function).
+ * Every rule of hyena_decode_sample then reads "A" where it reads "the live tokens": ranks are taken among A (a NaN first, then numbers by
+ * value, then by index), top_k <= 1 takes rank 0 of A, k = min(top_k, |A|), p_i = exp((l_i - max_A l) / T) summed in rank order, the nucleus
+ * is a prefix of that order, the draw is the same Philox word of (seed, row, column), and a row whose rank-0 logit within A is not finite
+ * emits that token.  eos ends a row when it is emitted, hence only where A holds it.  Parked and done rows behave as above; a done row
+ * writes next = pad and nothing else, its log-prob slot included.  (col[b], done[b] and start[b] are read for every row, together; a parked
+ * or done row's logits and masks are not.)  The emitted token is always in A.
+ * `logprobs` (row b at b ldp, fp32) or NULL: logprobs[b ldp + n] = (l_tok - m) - log(sum_{j < Vlive} exp(l_j - m)), m = max_{j < Vlive} l_j
+ * -- the model's own distribution over ALL live tokens at temperature 1, not the constrained or tempered one -- in fp32, the sum taken
+ * serially in index order (a pure function of the row's logits).  Where m or the sum is not finite (a live NaN or +inf, or every live logit
+ * -inf) the slot receives NaN; a token whose own logit is -inf among finite ones gets -inf.  Written only for n in [0, ldp).
+ * With allow == NULL and logprobs == NULL, or with every mask all ones, seq, next, col, done, scores and u_out equal hyena_decode_sample's
+ * bit for bit.  Bad arguments as for hyena_decode_sample, and: start == NULL with allow or logprobs given, nallow < 1 or 0 < lda < nallow
+ * with allow given, ldp < 1 with logprobs given. */
+int hyena_decode_sample_constrained(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
+                                    const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds,
+                                    int ncols, long long* next, long ldn, float* scores, float* u_out, const unsigned long long* allow,
+                                    long lda, int nallow, const int* start, float* logprobs, long ldp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
