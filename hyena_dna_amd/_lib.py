@@ -216,6 +216,17 @@ def lib():
         L.hyena_decode_sample_constrained.restype = c_int
         L.hyena_decode_sample_constrained.argtypes = L.hyena_decode_sample.argtypes[:-1] + [c_void_p, ctypes.c_long, c_int, c_void_p, c_void_p,
                                                                                            ctypes.c_long, c_void_p]
+        # beam search: the beam step, the fan-out cache's re-parenting, the backtrack
+        L.hyena_decode_beam.restype = c_int
+        L.hyena_decode_beam.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long, c_int, c_void_p, c_void_p,
+                                        c_void_p, ctypes.c_long, c_int, c_void_p]
+        L.hyena_decode_reorder_fan.restype = c_int
+        L.hyena_decode_reorder_fan.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_int, c_void_p]
+        L.hyena_decode_beam_backtrack.restype = c_int
+        L.hyena_decode_beam_backtrack.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p,
+                                                  ctypes.c_long, c_int, c_void_p, ctypes.c_long, c_void_p]
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -1195,6 +1206,85 @@ def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, t
                                         int(eos), int(pad), col.data_ptr(), done.data_ptr(), seq.data_ptr(), seq.stride(0) if B > 1 else ncols,
                                         ncols, nxt.data_ptr(), nxt.stride(0) if B > 1 else 1, None if scores is None else scores.data_ptr(),
                                         None if u_out is None else u_out.data_ptr(), _backend.stream(logits.device)))
+
+
+# ---- beam search over the fan-out layout (hyena_decode_beam, hyena_decode_reorder_fan, hyena_decode_beam_backtrack) ----------------------------
+DECODE_BEAM_MAX = 16         # HYENA_DECODE_BEAM_MAX: beams per prompt (the rows of a fan group)
+
+
+def _beam_rows(B, fan, *tensors):
+    assert 1 <= int(fan) <= DECODE_BEAM_MAX and B % int(fan) == 0
+    for t in tensors:
+        assert t.dtype == torch.int32 and t.shape == (B,) and t.is_contiguous()
+
+
+def decode_beam(logits, score, col, done, start, parent, nxt, fan, ncols, eos=-1, pad=0, vocab=None, allow=None, tok_hist=None, parent_hist=None,
+                lp_hist=None):
+    """The beam step: logits (B = G fan, V <= 64) fp32 / bf16 / fp16, rows contiguous; the ``fan`` rows of a group are the beams of one
+    prompt, best first.  ``score`` fp32 (B,) cumulative log-probabilities (0 / -inf ... before the first step); ``col`` / ``done`` /
+    ``start`` / ``parent``: device int32 (B,); ``nxt`` (B,) or (B, 1) int64.  Per group the ``fan`` best of {live row, allowed token} and
+    {finished row, pad} by score (then NaN scores; ties by row, then token) go to its rows in rank order: ``parent`` (absolute row),
+    ``score``, ``done``, ``nxt``, ``col`` + 1 and the records ``tok_hist`` / ``parent_hist`` (int32) / ``lp_hist`` (fp32), all (B, N'), at
+    [b, col[b] - start[b]].  A group whose column lies outside [0, ncols) is left alone.  ``allow``: as for ``decode_sample``."""
+    _require_gpu(logits, "logits")
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    _beam_rows(B, fan, col, done, start, parent)
+    assert score.dtype == torch.float32 and score.shape == (B,) and score.is_contiguous()
+    assert nxt.dtype == torch.int64 and nxt.numel() == B and nxt.shape[0] == B
+    assert allow is None or (allow.dtype == torch.int64 and allow.dim() in (1, 2) and allow.shape[-1] >= 1 and allow.is_contiguous()
+                             and (allow.dim() == 1 or allow.shape[0] == B))
+    recs = [t for t in (tok_hist, parent_hist, lp_hist) if t is not None]
+    for t in recs:
+        assert t.dim() == 2 and t.shape == (B, recs[0].shape[1]) and t.shape[1] >= 1 and t.is_contiguous()
+        assert t.dtype == (torch.float32 if t is lp_hist else torch.int32)
+    for t in [score, col, done, start, parent, nxt, allow] + recs:
+        assert t is None or t.device == logits.device
+    nrec = recs[0].shape[1] if recs else 0
+    with _backend.guard(logits.device):
+        check(lib().hyena_decode_beam(
+            logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, int(fan), V, V if vocab is None else int(vocab),
+            int(eos), int(pad), col.data_ptr(), done.data_ptr(), score.data_ptr(), start.data_ptr(), parent.data_ptr(), nxt.data_ptr(),
+            nxt.stride(0) if B > 1 else 1, int(ncols), None if allow is None else allow.data_ptr(),
+            0 if allow is None or allow.dim() == 1 else allow.shape[1], 0 if allow is None else allow.shape[-1],
+            None if tok_hist is None else tok_hist.data_ptr(), None if parent_hist is None else parent_hist.data_ptr(),
+            None if lp_hist is None else lp_hist.data_ptr(), nrec, nrec, _backend.stream(logits.device)))
+
+
+def decode_reorder_fan(hist_r, tail, parent, pos, B, fan, Lcap, S, c0):
+    """in place: hist_r[b, :, s - S] = old hist_r[parent[b], :, s - S] for c0 <= s < *pos, tail[:, b] = old tail[:, parent[b]] for every
+    row b < B (a parent outside b's group: b itself); nothing at all when *pos lies outside [S, Lcap]"""
+    _require_gpu(hist_r, "history")
+    Bcap, D, ldr = _hist(hist_r)
+    _beam_rows(int(B), fan, parent)
+    assert tail.dtype == torch.float32 and tail.shape == (3 * D, Bcap, 2) and tail.is_contiguous()
+    assert pos.dtype == torch.int32 and pos.numel() >= 1 and parent.device == hist_r.device == tail.device == pos.device
+    with _backend.guard(hist_r.device):
+        check(lib().hyena_decode_reorder_fan(hist_r.data_ptr(), tail.data_ptr(), parent.data_ptr(), pos.data_ptr(), int(B), Bcap, int(fan), D,
+                                             int(Lcap), int(S), int(c0), ldr, dtype_code(hist_r.dtype), _backend.stream(hist_r.device)))
+
+
+def decode_beam_backtrack(tok_hist, parent_hist, lp_hist, fan, n_done, n_ret, seq, P, logprobs=None):
+    """seq[g n_ret + r, P + i] (and logprobs[g n_ret + r, i]) for i < n_done: the tokens (log-probs) of the beam that ends in row g fan + r,
+    read off the records backwards through ``parent_hist``"""
+    _require_gpu(tok_hist, "tok_hist")
+    B = tok_hist.shape[0]
+    assert 1 <= int(fan) <= DECODE_BEAM_MAX and B % int(fan) == 0 and 1 <= int(n_ret) <= int(fan)
+    for t in (tok_hist, parent_hist):
+        assert t.dtype == torch.int32 and t.dim() == 2 and t.shape == tok_hist.shape and t.is_contiguous()
+    rows = B // int(fan) * int(n_ret)
+    assert seq.dtype == torch.int64 and seq.dim() == 2 and seq.shape[0] == rows and seq.stride(1) == 1 and seq.device == tok_hist.device
+    assert 0 <= int(n_done) <= tok_hist.shape[1] and int(P) >= 0 and seq.shape[1] >= int(P) + int(n_done)
+    if logprobs is not None:
+        assert lp_hist is not None and lp_hist.dtype == torch.float32 and lp_hist.shape == tok_hist.shape and lp_hist.is_contiguous()
+        assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.shape[0] == rows and logprobs.stride(1) == 1
+        assert logprobs.shape[1] >= max(int(n_done), 1) and logprobs.device == tok_hist.device
+    with _backend.guard(tok_hist.device):
+        check(lib().hyena_decode_beam_backtrack(
+            tok_hist.data_ptr(), parent_hist.data_ptr(), None if lp_hist is None else lp_hist.data_ptr(), tok_hist.stride(0), B, int(fan),
+            int(n_done), int(n_ret), seq.data_ptr(), seq.stride(0) if rows > 1 else seq.shape[1], int(P),
+            None if logprobs is None else logprobs.data_ptr(), 0 if logprobs is None else (logprobs.stride(0) if rows > 1 else logprobs.shape[1]),
+            _backend.stream(tok_hist.device)))
 
 
 # ---- input projection on the matrix cores with the front of the shell in its epilogue (include/hyena_proj.h) --------------------

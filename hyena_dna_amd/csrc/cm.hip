@@ -432,4 +432,58 @@ int hyena_decode_sample_constrained(const void* logits, long ldl, int dtype, int
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
+// ---- beam search (decode_beam_kernel, decode_reorder_fan_kernel, decode_beam_backtrack_kernel) ---------------------------------------------
+static_assert(BEAM_MAX == HYENA_DECODE_BEAM_MAX, "the header's beam limit");
+
+int hyena_decode_beam(const void* logits, long ldl, int dtype, int B, int fan, int V, int Vlive, int eos, int pad, int* col, int* done,
+                      float* beam_score, const int* start, int* parent, long long* next, long ldn, int ncols,
+                      const unsigned long long* allow, long lda, int nallow, int* tok_hist, int* parent_hist, float* lp_hist, long ldh,
+                      int nrec, void* stream) {
+    if (logits == nullptr || col == nullptr || done == nullptr || beam_score == nullptr || start == nullptr || parent == nullptr ||
+        next == nullptr || B < 1 || fan < 1 || fan > BEAM_MAX || B % fan != 0 || V < 1 || V > SMP_VMAX || Vlive < 1 || Vlive > V ||
+        !dec_dtype_ok(dtype) || ldl < V || ncols < 1 || ldn < 1)
+        return HYENA_ERR_BAD_ARG;
+    if (allow != nullptr && (nallow < 1 || (lda != 0 && lda < nallow))) return HYENA_ERR_BAD_ARG;
+    const bool rec = tok_hist != nullptr || parent_hist != nullptr || lp_hist != nullptr;
+    if (rec && (nrec < 1 || ldh < nrec)) return HYENA_ERR_BAD_ARG;
+    BeamArgs a;
+    a.logits = logits; a.score = beam_score; a.col = col; a.done = done; a.start = start; a.parent = parent; a.next = next;
+    a.allow = allow; a.tok_hist = tok_hist; a.parent_hist = parent_hist; a.lp_hist = lp_hist;
+    a.ldl = ldl; a.ldn = ldn; a.lda = lda; a.ldh = ldh;
+    a.B = B; a.fan = fan; a.V = V; a.Vlive = Vlive; a.ncols = ncols; a.eos = eos; a.pad = pad;
+    a.nallow = allow != nullptr ? nallow : 0; a.nrec = rec ? nrec : 0;
+    const int G = B / fan;
+    HY_DEC_DISPATCH(decode_beam_kernel, dim3(G < SMP_MAX_GRID ? G : SMP_MAX_GRID), SMP_VMAX, BEAM_LDS_BYTES);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_reorder_fan(void* vgr, float* tail, const int* parent, const int* pos, int B, int Bcap, int fan, int D, int Lcap, int S,
+                             int c0, int ldr, int dtype, void* stream) {
+    if (tail == nullptr || parent == nullptr || pos == nullptr || !dec_fan_ok(false, nullptr, vgr, B, fan, D, Lcap, S, 0, ldr, dtype) ||
+        fan > BEAM_MAX || Bcap < B || c0 < S || c0 > Lcap)
+        return HYENA_ERR_BAD_ARG;
+    ReorderArgs a;
+    a.vg = vgr; a.tail = tail; a.parent = parent; a.pos = pos;
+    a.B = B; a.Bcap = Bcap; a.fan = fan; a.D = D; a.Lcap = Lcap; a.S = S; a.c0 = c0; a.lda = ldr;
+    const size_t items = (size_t)(B / fan) * D * ((size_t)(Lcap - c0) + 6);
+    const size_t blocks = (items + DEC_THREADS - 1) / DEC_THREADS;
+    HY_DEC_DISPATCH(decode_reorder_fan_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), DEC_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_decode_beam_backtrack(const int* tok_hist, const int* parent_hist, const float* lp_hist, long ldh, int B, int fan, int n_done,
+                                int n_ret, long long* seq, long lds, int P, float* logprobs, long ldp, void* stream) {
+    if (tok_hist == nullptr || parent_hist == nullptr || seq == nullptr || B < 1 || fan < 1 || fan > BEAM_MAX || B % fan != 0 || n_ret < 1 ||
+        n_ret > fan || n_done < 0 || ldh < n_done || ldh < 1 || P < 0 || lds < (long)P + n_done ||
+        (logprobs != nullptr && (lp_hist == nullptr || ldp < n_done || ldp < 1)))
+        return HYENA_ERR_BAD_ARG;
+    BacktrackArgs a;
+    a.tok_hist = tok_hist; a.parent_hist = parent_hist; a.lp_hist = lp_hist; a.seq = seq; a.logprobs = logprobs;
+    a.ldh = ldh; a.lds = lds; a.ldp = ldp;
+    a.B = B; a.fan = fan; a.n_done = n_done; a.n_ret = n_ret; a.P = P;
+    const int rows = B / fan * n_ret;
+    HY_LAUNCH(decode_beam_backtrack_kernel, dim3((rows + DEC_THREADS - 1) / DEC_THREADS), dim3(DEC_THREADS), 0, stream, a);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
 }  // extern "C"

@@ -13,6 +13,8 @@
 // The position t lives in device memory and all three kernels read it there: one captured graph serves every position.
 // Variants further down: one position per row (_rows), n continuations of one prompt (_fan), T known positions per call (_block), and the
 // lookahead carry (_carry, _la): the history's share of the next W outputs taken once per W positions, so that a step reads W + 7 columns.
+// At the end of the file: token sampling (plain and constrained) and beam search over the fan-out layout (the beam step, the cache's
+// re-parenting, the backtrack).
 //
 // The two streams of decode_conv run in opposite directions (vg forward in s, k backward), and the k stream is misaligned by t mod 4 words
 // relative to the vg stream.  The history is the operand that scales with B, so ITS loads stay aligned 16-byte vectors (8 elements per lane at
@@ -1096,6 +1098,288 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConAr
                 a.logprobs[(size_t)b * a.ldp + n] = ok ? (ltok - lmax) - logf(lsum) : __builtin_nanf("");
             }
         }
+    }
+}
+
+// ---- beam search: the beam step, the cache reorder, the backtrack (C ABI: hyena_decode_beam, _reorder_fan, _beam_backtrack) ------------------
+// The k beams of a prompt are the k = `fan` rows of a fan group (row g k + r: rank r of prompt g, best first).  The beam step takes the
+// sampler's place as the last compute node of a step: one wavefront per group, grid-stride over the groups, all of its state in device
+// memory.  With c = col[g k] (one column per group; outside [0, ncols): parked, nothing of the group is read or written):
+//   log-prob    of a live row j: lp[j][i] = (l_i - m) - log(sum_{v < Vlive} exp(l_v - m)), decode_sample_con_kernel's value operation for
+//               operation (m by fmaxf in index order, NaNs skipped; the terms expf(l_v - m) summed serially in index order; NaN where m or
+//               the sum is not finite).  Lane j walks row j's 64 LDS slots alone -- the k rows' serial scans run side by side.
+//   candidates  a live row: every token i of its allowed set A (decode_sample_con_kernel's, the empty-mask rule included) with score
+//               beam_score[j] + lp[j][i]; a finished row: ONE candidate, token `pad`, its score unchanged, in slot i = 0.
+//   selection   the first k candidates in the order: numbers by score descending (-inf is a number), then NaNs; ties -- equal scores, or
+//               two NaNs -- by the flat index j V + i ascending.  A total order for every input.  k rounds: every lane offers the best
+//               candidate left in its column i (its k slots are its own), a butterfly of six exchanges over the wavefront leaves the
+//               first of the 64 offers in every lane (the order is total: one winner whatever the reduction's shape), its lane
+//               strikes it out.  No barrier inside a round.  (A serial scan of the 64 offers from LDS by every lane, the first
+//               version, made the kernel 54 us at k = 8 by kernel trace, twelve times the sampler's.)
+//   writes      rank r goes to row g k + r: parent (the absolute row of the candidate), beam_score, done (the parent's, or 1 on eos), next
+//               (the token; pad for a finished row), col = c + 1, and the records tok_hist / parent_hist / lp_hist [b, n], n = c - start[b],
+//               for n inside [0, nrec) (lp of a finished row's pad: 0, so that a beam's records sum to its score).  Lane 0 writes, after
+//               the barriers, i.e. after every lane has read the group's state: the sampler's single-writer rule.  No atomics.
+// Every row yields a candidate, so k exist; should none be left all the same (it cannot happen), the round yields the row itself with
+// `pad` and a NaN score: the kernel stays total.  Every branch around a barrier is taken on col[g k], fan or the loop counters: uniform.
+enum { BEAM_MAX = 16, BEAM_LD = SMP_VMAX + 1 /* row pitch in LDS: lane j walks row j, one bank apart */,
+       BEAM_LDS_BYTES = (2 * BEAM_MAX * BEAM_LD + 11 * BEAM_MAX) * 4 };
+
+struct BeamArgs {
+    const void* logits;               // (B, V) I/O type, row b at b ldl
+    float* score;                     // (B,) fp32 cumulative log-probability of the beam in row b
+    int* col;                         // (B,) the column row b writes next (one value per group)
+    int* done;                        // (B,) set once the beam in row b has emitted eos
+    const int* start;                 // (B,) the column of row b's first new token
+    int* parent;                      // (B,) out: the row this step's row b continues
+    long long* next;                  // (B,) the model's next input ids, element b at b ldn
+    const unsigned long long* allow;  // (B or 1, nallow) bit masks, row b at b lda, or null
+    int* tok_hist;                    // (B, nrec) records, row b at b ldh, or null
+    int* parent_hist;
+    float* lp_hist;
+    long ldl, ldn, lda, ldh;
+    int B, fan, V, Vlive, ncols, eos, pad, nallow, nrec;
+};
+
+// "a comes before b" in the selection order; ia, ib: flat indices
+__device__ __forceinline__ bool beam_before(float sa, int ia, float sb, int ib) {
+    const bool an = sa != sa, bn = sb != sb;
+    if (an || bn) return an == bn ? ia < ib : bn;
+    return sa > sb || (sa == sb && ia < ib);
+}
+
+__device__ __forceinline__ uint32_t beam_f32_bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, 4); return u; }
+__device__ __forceinline__ float beam_bits_f32(uint32_t u) { float v; __builtin_memcpy(&v, &u, 4); return v; }
+
+template <int DT>
+__global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    HY_SMEM(smem);
+    HY_LDS float* sl = HY_LDS_CAST(float, smem);                 // [k][BEAM_LD] live logits by (row, index); then the candidates' scores
+    HY_LDS float* se = sl + BEAM_MAX * BEAM_LD;                  // [k][BEAM_LD] exp(l - max l); then the candidates' log-probs
+    HY_LDS float* smax = se + BEAM_MAX * BEAM_LD;                // [k] max of the live logits of row j
+    HY_LDS float* ssum = smax + BEAM_MAX;                        // [k] sum of the terms of row j
+    HY_LDS float* rs = ssum + BEAM_MAX;                          // [k] result: score of rank r
+    HY_LDS float* rl = rs + BEAM_MAX;                            // [k] result: log-prob of rank r's token
+    HY_LDS int* sfin = HY_LDS_CAST(int, rl + BEAM_MAX);          // [k] done flag of row j
+    HY_LDS int* rp = sfin + BEAM_MAX;                            // [k] result: row of rank r within the group
+    HY_LDS int* rt = rp + BEAM_MAX;                              // [k] result: token of rank r
+    HY_LDS int* rd = rt + BEAM_MAX;                              // [k] result: done flag of rank r
+    HY_LDS float* ssc = HY_LDS_CAST(float, rd + BEAM_MAX);       // [k] beam_score of row j
+    HY_LDS int* sAlo = rd + 2 * BEAM_MAX;                        // [k] allowed set of row j, low and high word
+    HY_LDS int* sAhi = sAlo + BEAM_MAX;
+    const int i = threadIdx.x, k = a.fan;
+    const float ninf = -__builtin_inff();
+    const unsigned long long all = a.Vlive >= 64 ? ~0ull : (1ull << a.Vlive) - 1ull;
+    const bool live = i < a.Vlive;
+    const int G = a.B / k;
+    for (long g = blockIdx.x; g < G; g += gridDim.x) {
+        const long b0 = g * k;
+        const int c = a.col[b0];
+        if (c < 0 || c >= a.ncols) continue;                     // parked (uniform: one address for the wavefront)
+        __syncthreads();                                         // the previous group's results have been read by lane 0
+        // the rows' logits by (row, index); lane j keeps row j's state
+        for (int j = 0; j < k; ++j) {
+            const float l = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.logits)[(size_t)(b0 + j) * a.ldl + (i < a.V ? i : 0)]);
+            sl[j * BEAM_LD + i] = live ? l : ninf;
+        }
+        float sc_row = 0.f;                                      // lane j < k: beam_score, done, mask of row j
+        int fin_row = 0;
+        unsigned long long A_row = all;
+        if (i < k) {
+            sc_row = a.score[b0 + i];
+            fin_row = a.done[b0 + i];
+            const long n = (long)c - a.start[b0 + i];
+            if (a.allow != nullptr && n >= 0 && n < a.nallow) {
+                const unsigned long long m = a.allow[(size_t)(b0 + i) * a.lda + n] & all;
+                if (m != 0ull) A_row = m;
+            }
+            sfin[i] = fin_row;
+            ssc[i] = sc_row;
+            sAlo[i] = (int)A_row;
+            sAhi[i] = (int)(A_row >> 32);
+        }
+        __syncthreads();
+        if (i < k) {
+            float lmax = ninf;
+            for (int v = 0; v < a.Vlive; ++v) lmax = fmaxf(lmax, sl[i * BEAM_LD + v]);      // over ALL live tokens, NaNs skipped
+            smax[i] = lmax;
+        }
+        __syncthreads();
+        for (int j = 0; j < k; ++j) se[j * BEAM_LD + i] = live ? expf(sl[j * BEAM_LD + i] - smax[j]) : 0.f;
+        __syncthreads();
+        if (i < k) {
+            float lsum = 0.f;
+            for (int v = 0; v < a.Vlive; ++v) lsum += se[i * BEAM_LD + v];                   // serially in index order
+            ssum[i] = lsum;
+        }
+        __syncthreads();
+        // the candidates of column i: slot (j, i) of sl receives the score, of se the log-prob; `mine`: bit j -- candidate (j, i) is in the race
+        unsigned mine = 0u;
+        for (int j = 0; j < k; ++j) {
+            const float sj = ssc[j];
+            const unsigned long long Aj = ((unsigned long long)(unsigned)sAhi[j] << 32) | (unsigned)sAlo[j];
+            const float lmax = smax[j], lsum = ssum[j];
+            const bool ok = lmax - lmax == 0.f && lsum - lsum == 0.f;
+            const float lp = ok ? (sl[j * BEAM_LD + i] - lmax) - logf(lsum) : __builtin_nanf("");
+            const bool fin = sfin[j] != 0;
+            const bool in = fin ? i == 0 : (((Aj >> i) & 1ull) != 0ull);
+            sl[j * BEAM_LD + i] = fin ? sj : sj + lp;
+            se[j * BEAM_LD + i] = fin ? 0.f : lp;
+            mine |= in ? 1u << j : 0u;
+        }
+        __syncthreads();                                         // (lane 0 reads the winners' log-probs out of other lanes' slots)
+        for (int r = 0; r < k; ++r) {
+            float best = 0.f;
+            int bestj = -1;
+            for (int j = 0; j < k; ++j) {
+                const float s = sl[j * BEAM_LD + i];
+                if (((mine >> j) & 1u) != 0u && (bestj < 0 || beam_before(s, j, best, bestj))) {      // (one column: the flat index orders as j)
+                    best = s;
+                    bestj = j;
+                }
+            }
+            // the first of the 64 offers in the selection order, by a butterfly over the wavefront: the order is total and the flat indices
+            // differ, so the minimum is one candidate whatever the shape of the reduction, and after six exchanges every lane holds it
+            float win = best;
+            int wflat = bestj < 0 ? -1 : bestj * a.V + i;
+            HY_UNROLL
+            for (int m = SMP_VMAX / 2; m >= 1; m >>= 1) {
+                const float so = beam_bits_f32(HY_SHFL_U32(beam_f32_bits(win), i ^ m));
+                const int fo = (int)HY_SHFL_U32((uint32_t)wflat, i ^ m);
+                if (fo >= 0 && (wflat < 0 || beam_before(so, fo, win, wflat))) {
+                    win = so;
+                    wflat = fo;
+                }
+            }
+            const int winj = wflat < 0 ? -1 : wflat / a.V, wini = wflat < 0 ? 0 : wflat % a.V;
+            if (winj >= 0 && i == wini) mine &= ~(1u << winj);
+            if (i == 0) {
+                const bool none = winj < 0;                      // (cannot happen: every row yields a candidate)
+                const int pj = none ? r : winj;
+                const bool fin = none || sfin[pj] != 0;
+                const int tok = fin ? a.pad : wini;
+                rp[r] = pj;
+                rt[r] = tok;
+                rs[r] = none ? __builtin_nanf("") : win;
+                rl[r] = none ? 0.f : se[pj * BEAM_LD + wini];
+                rd[r] = (sfin[pj] != 0 || (!fin && tok == a.eos)) ? 1 : 0;
+            }
+        }
+        // (lane 0 wrote the results itself; every lane's reads of score / done / start / col lie before the barriers above)
+        if (i == 0) {
+            for (int r = 0; r < k; ++r) {
+                const long b = b0 + r;
+                const long n = (long)c - a.start[b];
+                a.parent[b] = (int)(b0 + rp[r]);
+                a.score[b] = rs[r];
+                a.done[b] = rd[r];
+                a.next[(size_t)b * a.ldn] = rt[r];
+                a.col[b] = c + 1;
+                if (n >= 0 && n < a.nrec) {
+                    if (a.tok_hist != nullptr) a.tok_hist[(size_t)b * a.ldh + n] = rt[r];
+                    if (a.parent_hist != nullptr) a.parent_hist[(size_t)b * a.ldh + n] = (int)(b0 + rp[r]);
+                    if (a.lp_hist != nullptr) a.lp_hist[(size_t)b * a.ldh + n] = rl[r];
+                }
+            }
+        }
+    }
+}
+
+// Re-parenting the rows of one layer's fan-out cache in place: with t1 = *pos (the position decode_post_fan left) and c0 the first column
+// that can differ between the rows of a group (the prompt length),
+//     vgr[b, d, s - S] = old vgr[parent[b], d, s - S]  for c0 <= s < t1,      tail[c, b, :] = old tail[c, parent[b], :]  for c < 3 D
+// for every row b; a parent outside b's own group counts as b.  t1 outside [S, Lcap]: nothing is written.  The shared tensor, the columns
+// below c0 and those from t1 on are never touched.  In place without scratch or a second launch: ONE thread owns one (group, channel,
+// column) -- or one (group, tail element) -- for all k rows: it loads the k values through parent[] into registers (the loop is fully
+// unrolled to BEAM_MAX with a predicate on j < fan: the address is dynamic, the register index is not), and only then stores them.  No
+// other thread reads or writes those addresses.  Consecutive threads take consecutive columns of one row: the accesses coalesce; c0 - S
+// has no alignment, so the loads and stores are single elements of the I/O type.  The grid comes from Lcap - c0 on the host with a
+// grid-stride loop, the live range from *pos: one captured launch serves every token.
+// Bytes per layer and step: 2 B D (t1 - c0) sizeof(io) (+ 2 * 6 B D * 4 for the tails) -- linear in the number of new tokens, independent
+// of the prompt.
+struct ReorderArgs {
+    void* vg;                         // per-row history (Bcap, D, lda) I/O type, column s at s - S
+    float* tail;                      // (3D, Bcap, 2) fp32
+    const int* parent;                // (B,)
+    const int* pos;                   // t1
+    int B, Bcap, fan, D, Lcap, S, c0, lda;
+};
+
+template <int DT>
+__global__ void __launch_bounds__(DEC_THREADS) decode_reorder_fan_kernel(ReorderArgs a) {
+    typedef typename Elem<DT>::type elem_t;
+    const int t1 = a.pos[0];
+    if (t1 < a.S || t1 > a.Lcap) return;
+    const int k = a.fan;
+    const size_t W = (size_t)(a.Lcap - a.c0);                    // columns a thread index can stand for
+    const size_t nh = (size_t)(a.B / k) * a.D * W, nt = (size_t)(a.B / k) * a.D * 6;
+    elem_t* vg = reinterpret_cast<elem_t*>(a.vg);
+    for (size_t idx = (size_t)blockIdx.x * DEC_THREADS + threadIdx.x; idx < nh + nt; idx += (size_t)gridDim.x * DEC_THREADS) {
+        if (idx < nh) {
+            const int s = a.c0 + (int)(idx % W);
+            if (s >= t1) continue;
+            const size_t gd = idx / W;
+            const int g = (int)(gd / a.D), d = (int)(gd % a.D);
+            const int b0 = g * k;
+            const size_t off = (size_t)d * a.lda + (size_t)(s - a.S);
+            elem_t v[BEAM_MAX];
+            HY_UNROLL
+            for (int j = 0; j < BEAM_MAX; ++j) {
+                if (j < k) {
+                    int p = a.parent[b0 + j];
+                    if (p < b0 || p >= b0 + k) p = b0 + j;
+                    v[j] = vg[(size_t)p * a.D * a.lda + off];
+                }
+            }
+            HY_UNROLL
+            for (int j = 0; j < BEAM_MAX; ++j)
+                if (j < k) vg[(size_t)(b0 + j) * a.D * a.lda + off] = v[j];
+        } else {
+            const size_t q = idx - nh;                            // (g, c, e): consecutive threads, consecutive floats of one tail row
+            const int e = (int)(q % 2);
+            const size_t gc = q / 2;
+            const int c = (int)(gc % (3 * (size_t)a.D)), g = (int)(gc / (3 * (size_t)a.D));
+            const int b0 = g * k;
+            float* row = a.tail + (size_t)c * a.Bcap * 2 + e;
+            float v[BEAM_MAX];
+            HY_UNROLL
+            for (int j = 0; j < BEAM_MAX; ++j) {
+                if (j < k) {
+                    int p = a.parent[b0 + j];
+                    if (p < b0 || p >= b0 + k) p = b0 + j;
+                    v[j] = row[(size_t)p * 2];
+                }
+            }
+            HY_UNROLL
+            for (int j = 0; j < BEAM_MAX; ++j)
+                if (j < k) row[(size_t)(b0 + j) * 2] = v[j];
+        }
+    }
+}
+
+// After the last step: one thread per returned row q = g n_ret + r walks the records from step n_done - 1 back to step 0, starting at row
+// g k + r (rank r of group g): token and log-prob of step i from the row it stands in, then on to that row's parent of step i (a parent
+// outside [0, B) counts as the row itself).  seq[q, P + i] and, where asked for, logprobs[q, i] for i < n_done.
+struct BacktrackArgs {
+    const int* tok_hist;              // (B, >= n_done) records, row b at b ldh
+    const int* parent_hist;
+    const float* lp_hist;             // or null
+    long long* seq;                   // (G n_ret, >= P + n_done), row q at q lds
+    float* logprobs;                  // (G n_ret, >= n_done), row q at q ldp, or null
+    long ldh, lds, ldp;
+    int B, fan, n_done, n_ret, P;
+};
+
+__global__ void __launch_bounds__(DEC_THREADS) decode_beam_backtrack_kernel(BacktrackArgs a) {
+    const long q = (long)blockIdx.x * DEC_THREADS + threadIdx.x;
+    if (q >= (long)(a.B / a.fan) * a.n_ret) return;
+    long b = q / a.n_ret * a.fan + q % a.n_ret;
+    for (int i = a.n_done - 1; i >= 0; --i) {
+        a.seq[(size_t)q * a.lds + a.P + i] = a.tok_hist[(size_t)b * a.ldh + i];
+        if (a.logprobs != nullptr) a.logprobs[(size_t)q * a.ldp + i] = a.lp_hist[(size_t)b * a.ldh + i];
+        const int p = a.parent_hist[(size_t)b * a.ldh + i];
+        if (p >= 0 && p < a.B) b = p;
     }
 }
 

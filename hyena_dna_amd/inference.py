@@ -309,6 +309,29 @@ class HyenaDecodeState:
         _lib.decode_post_block(part, self.hist, self.fb, x0, z, self.pos, self.L)
         return z
 
+    def reorder(self, parents):
+        """This package's ``_reorder_cache``: row b of the cache continues as what row ``parents[b]`` was.  ``parents``: device int32
+        (B,), every entry a row of b's own fan group (an entry outside it leaves row b as it is).  In place, one kernel on the current
+        stream that reads the position from device memory -- it may be captured with the step.  It moves the columns written since the
+        prompt and the short filter's tail, ``2 B D (t - prompt_len)`` elements in all: the prompt's columns are the same in every row of
+        a group (``hist_shared`` below S, replicated by the prefill from S on) and stay where they are, however long the prompt is.
+
+        Fan-out caches only: the rows of a plain cache share nothing, and a caller who wants to prune, resample or branch rows builds the
+        cache with ``fan=n``.  Ragged caches and caches with lookahead are refused likewise, before anything moves."""
+        if self.W:
+            raise NotImplementedError("reorder() on a cache with lookahead is out of scope: the carry belongs to its row's history")
+        if self.ragged:
+            raise NotImplementedError("reorder() on a ragged cache (prefill with lengths) is out of scope: one position per row")
+        if self.fan == 1:
+            raise NotImplementedError("reorder() re-parents the rows of a fan group: build the cache with fan=n (a cache with fan = 1 has "
+                                      "no groups)")
+        if not torch.is_tensor(parents) or parents.dtype != torch.int32 or parents.shape != (self.B,) or parents.device != self.hist.device:
+            what = f"{tuple(parents.shape)} {parents.dtype} on {parents.device}" if torch.is_tensor(parents) else type(parents).__name__
+            raise ValueError(f"parents must be a ({self.B},) int32 tensor on {self.hist.device} (got {what})")
+        if self.fan > _lib.DECODE_BEAM_MAX:
+            raise NotImplementedError(f"reorder() serves groups of at most {_lib.DECODE_BEAM_MAX} rows (this cache has fan = {self.fan})")
+        _lib.decode_reorder_fan(self.hist, self.tail, parents.contiguous(), self.pos, self.B, self.fan, self.L, self.S, self.prompt_len)
+
 
 class DeviceSampler:
     """The token sampler of cached generation as one kernel per step (csrc/decode_kernels.h decode_sample_kernel; semantics in
@@ -366,6 +389,86 @@ class DeviceSampler:
             if logprobs is not None:
                 self.logprobs.scatter_(1, pidx, logprobs)
         return restore
+
+
+class BeamSearcher:
+    """Beam search over a fan-out cache as the counterpart of ``DeviceSampler``, with its call protocol: ``searcher(logits, nxt)`` runs the
+    beam kernel (csrc/decode_kernels.h decode_beam_kernel; semantics in include/hyena_decode.h) on ``logits`` (G k, V <= 64) and then
+    ``reorder(parent)`` on every layer's cache, all on the current stream and with nothing read on the host.
+    ``GraphedDecodeStep(model, ip, G * k, sampler=searcher)`` therefore captures the model step, the beam step and the n_layer reorders
+    as one graph.
+
+    ``states``: the ``HyenaDecodeState`` of every layer, built with ``fan=k, prompt_len=P`` (``ip.key_value_memory_dict.values()``), after
+    the prefill.  The k rows of group g are the beams of prompt g, best first.  State, all in device memory: ``score`` (fp32 cumulative
+    log-probability, 0 / -inf before the first call so that the k identical rows expand as one), ``done``, ``col``, ``parent`` (the last
+    step's parents) and the records ``tok_hist`` / ``parent_hist`` / ``lp_hist`` (G k, n_new), which ``finalize`` reads backwards."""
+
+    def __init__(self, states, prompts, k, n_new, eos=None, pad=0, vocab=None, allow=None):
+        self.states = list(states)
+        self.prompts = prompts                                   # (G, P) int64
+        G, P = prompts.shape
+        dev = prompts.device
+        self.G, self.k, self.P, self.N = G, int(k), P, int(n_new)
+        if not 1 <= self.k <= _lib.DECODE_BEAM_MAX:
+            raise ValueError(f"a beam search keeps 1 ... {_lib.DECODE_BEAM_MAX} beams per prompt (got {k})")
+        for s in self.states:
+            if s.fan != self.k or s.B != G * self.k or getattr(s, "prompt_len", None) != P:
+                raise ValueError(f"the decode caches must be built with fan = {self.k} for {G} prompts of {P} positions")
+        B = G * self.k
+        self.eos, self.pad, self.vocab, self.allow = (-1 if eos is None else int(eos)), int(pad), vocab, allow
+        self.col = torch.full((B,), P, dtype=torch.int32, device=dev)
+        self.start = self.col.clone()
+        self.done = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.score = torch.full((G, self.k), float("-inf"), dtype=torch.float32, device=dev)
+        self.score[:, 0] = 0.0
+        self.score = self.score.reshape(B)
+        self.parent = torch.arange(B, dtype=torch.int32, device=dev)
+        width = max(self.N, 1)
+        self.tok_hist = torch.full((B, width), self.pad, dtype=torch.int32, device=dev)
+        self.parent_hist = self.parent[:, None].repeat(1, width).contiguous()
+        self.lp_hist = torch.zeros(B, width, dtype=torch.float32, device=dev)
+        self.calls = 0                                            # calls issued from the host (a replayed graph does not count)
+
+    def __call__(self, logits, nxt):
+        _lib.decode_beam(logits, self.score, self.col, self.done, self.start, self.parent, nxt, self.k, self.P + self.N, eos=self.eos,
+                         pad=self.pad, vocab=self.vocab, allow=self.allow, tok_hist=self.tok_hist, parent_hist=self.parent_hist,
+                         lp_hist=self.lp_hist)
+        for s in self.states:
+            s.reorder(self.parent)
+        self.calls += 1
+
+    def snapshot(self, steps):
+        """what up to ``steps`` calls from here may change, as a function that puts it back (``GraphedDecodeStep``'s warm-up steps run the
+        real kernels): the searcher's own state and, for every layer, the history columns [P, P + calls so far + steps) that the warm-up's
+        reorders permute (``GraphedDecodeStep`` restores ``tail`` and ``pos`` itself, before it calls this)"""
+        own = [(t, t.clone()) for t in (self.score, self.col, self.done, self.parent, self.tok_hist, self.parent_hist, self.lp_hist)]
+        calls = self.calls
+        hist = []
+        for s in self.states:
+            lo = self.P - s.S
+            hi = min(lo + calls + int(steps), s.L - s.S)
+            hist.append((s.hist[:, :, lo:hi], s.hist[:, :, lo:hi].clone()))
+
+        def restore():
+            for t, saved in own + hist:
+                t.copy_(saved)
+            self.calls = calls
+        return restore
+
+    def finalize(self, n_done, n_return=None, want_logprobs=False):
+        """after ``n_done`` calls: the ``n_return`` (default k) best beams of every prompt, best first -> ``sequences`` (G n_return, P + N)
+        int64 (the prompt, the beam's tokens, ``pad`` from column P + n_done on), ``sequences_scores`` (G n_return,) fp32, and
+        ``logprobs`` (G n_return, n_done) fp32 or None"""
+        n = self.k if n_return is None else int(n_return)
+        if not 1 <= n <= self.k:
+            raise ValueError(f"n_return={n_return}: 1 ... {self.k} of the beams")
+        dev = self.prompts.device
+        seq = torch.full((self.G * n, self.P + self.N), self.pad, dtype=torch.int64, device=dev)
+        seq[:, :self.P] = self.prompts.repeat_interleave(n, 0)
+        lp = torch.zeros(self.G * n, max(int(n_done), 1), dtype=torch.float32, device=dev) if want_logprobs else None
+        _lib.decode_beam_backtrack(self.tok_hist, self.parent_hist, self.lp_hist, self.k, n_done, n, seq, self.P, logprobs=lp)
+        scores = self.score.view(self.G, self.k)[:, :n].reshape(-1).clone()
+        return seq, scores, (None if lp is None else lp[:, :int(n_done)])
 
 
 # ---- allowed-token masks for the device sampler: pure host code ----------------------------------------------------------------------------

@@ -417,7 +417,7 @@ class GenerationMixin:
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
                  cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
                  stop_check_every=0, num_return_sequences=1, lookahead=None, allowed_tokens=None, constraints=None, min_new_tokens=0,
-                 output_logprobs=False, **kwargs):
+                 output_logprobs=False, num_beams=None, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
@@ -458,7 +458,29 @@ class GenerationMixin:
         read-back): a position that allows no token below ``vocab_size`` is a ValueError.  ``output_logprobs=True`` adds ``logprobs``
         (B, number of steps run) fp32 to the returned tuple: the log-probability of every emitted token under the softmax of its live
         logits at temperature 1 -- the model's own distribution, not the constrained or tempered one -- NaN where the logits hold a NaN
-        or +inf and for the positions of a finished row."""
+        or +inf and for the positions of a finished row.
+
+        ``num_beams=k`` (2 ... 16; None / 1: everything above, launch for launch): beam search -- the k most likely continuations found by
+        keeping the k best prefixes per prompt at every step, scored by the sum of their tokens' log-probabilities under the model
+        (temperature 1, all live tokens: the ``logprobs`` above).  ``input_ids`` (G, P); the cache is a fan-out cache with ``fan=k``, the
+        beams of prompt g being its rows g k ... g k + k - 1: one prefill over the G prompts, then per token one step that ends with
+        the beam kernel and one re-parenting of every layer's cache (``inference.BeamSearcher``, ``HyenaDecodeState.reorder``), which moves
+        the columns written since the prompt only.  With ``cg=True`` the N - 1 steps are N - 1 replays of one graph.  Returned: the
+        ``num_return_sequences = n <= k`` best beams per prompt, best first, row g n + r being rank r of prompt g; the tuple carries
+        ``sequences`` (G n, max_length), ``scores=None``, ``sequences_scores`` (G n,) fp32 and, with ``output_logprobs=True``,
+        ``logprobs`` (G n, steps run), whose rows sum to the scores.  Served with beams: ``allowed_tokens``, ``constraints`` ((N,) or
+        (G, N)), ``min_new_tokens``, ``eos_token_id`` (a finished beam keeps its score, holds ``pad_token_id`` from there on and competes
+        as it is), ``pad_token_id``, ``vocab_size``, ``stop_check_every``, ``cg``.  A beam that no allowed token can continue with a
+        finite probability has score -inf.  Refused: ``use_cache=False``, ``sampler="torch"``, ``top_k > 1``, ``top_p != 1``,
+        ``temperature != 1``, ``seed``, ``output_scores``, ``lengths``, ``lookahead``, n > k, logits of more than 64 columns.  Out of
+        scope: a length penalty or any length normalisation, diverse or sampled beams, beams on ragged or lookahead caches."""
+        if num_beams is not None and int(num_beams) != 1:
+            return self._generate_beam(input_ids, max_length, int(num_beams), int(num_return_sequences), top_k=top_k, temperature=temperature,
+                                       return_dict_in_generate=return_dict_in_generate, output_scores=output_scores, use_cache=use_cache,
+                                       cg=cg, lengths=lengths, pad_token_id=pad_token_id, top_p=top_p, eos_token_id=eos_token_id, seed=seed,
+                                       vocab_size=vocab_size, sampler=sampler, stop_check_every=int(stop_check_every), lookahead=lookahead,
+                                       allowed_tokens=allowed_tokens, constraints=constraints, min_new_tokens=min_new_tokens,
+                                       output_logprobs=output_logprobs)
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
         from .inference import check_lookahead
@@ -639,6 +661,100 @@ class GenerationMixin:
             fields.append("logprobs")
             values.append(torch.empty(B, 0, device=dev) if smp is None else smp.logprobs[:, :n_done].contiguous())
         return namedtuple("GreedySearchDecoderOnlyOutput", fields)(*values)
+
+
+    def _generate_beam(self, input_ids, max_length, k, n, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False,
+                       use_cache=False, cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None,
+                       sampler=None, stop_check_every=0, lookahead=None, allowed_tokens=None, constraints=None, min_new_tokens=0,
+                       output_logprobs=False):
+        """generate(num_beams=k): the prefill over the G prompts into a fan-out cache (fan = k), one eager beam step on its last logits,
+        then N - 1 steps that each end with the beam kernel and the caches' re-parenting (``inference.BeamSearcher``) -- with ``cg`` N - 1
+        graph replays -- and one backtrack over the records.  Every refusal comes before a cache is built."""
+        from . import _lib
+        from .inference import BeamSearcher, InferenceParams, check_lookahead
+        if not 2 <= k <= _lib.DECODE_BEAM_MAX:
+            raise ValueError(f"num_beams={k}: 2 ... {_lib.DECODE_BEAM_MAX} beams per prompt (None or 1: no beam search)")
+        if not use_cache:
+            raise ValueError("generate(num_beams=k) keeps the beams in a fan-out decode cache: it needs use_cache=True")
+        if sampler not in (None, "device"):
+            raise ValueError(f"generate(num_beams=k) with sampler={sampler!r}: the beam step is a device kernel (sampler='device' or None)")
+        if not 1 <= n <= k:
+            raise ValueError(f"num_return_sequences={n}: 1 ... num_beams = {k} of the beams can be returned")
+        nothing = [name for name, on in (("top_k > 1", int(top_k) > 1), ("top_p != 1", top_p is not None and float(top_p) != 1.0),
+                                         ("temperature != 1", float(temperature) != 1.0), ("seed", seed is not None),
+                                         ("output_scores", bool(output_scores))) if on]
+        if nothing:
+            raise ValueError(f"generate(num_beams=k) is a deterministic search on the model's own log-probabilities: it does not serve "
+                             f"{', '.join(nothing)}")
+        if lengths is not None:
+            raise NotImplementedError("generate(num_beams=k, lengths=...): beams on ragged caches are out of scope")
+        if check_lookahead(lookahead):
+            raise NotImplementedError("generate(num_beams=k, lookahead=W): beams on lookahead caches are out of scope")
+        if stop_check_every < 0:
+            raise ValueError(f"stop_check_every={stop_check_every}: a number of tokens, or 0 for never")
+        head = getattr(self, "lm_head", None)
+        V = head.weight.shape[0] if torch.is_tensor(getattr(head, "weight", None)) else None
+        if V is not None and V > _lib.SAMPLE_MAX_V:
+            raise ValueError(f"generate(num_beams=k) serves logits of at most {_lib.SAMPLE_MAX_V} columns (this model has {V})")
+        if vocab_size is not None and V is not None and not 1 <= int(vocab_size) <= V:
+            raise ValueError(f"vocab_size={vocab_size}: the logits have {V} columns")
+        dev = input_ids.device
+        if not (dev.type == "cuda" or _lib._backend.name != "hip"):
+            raise NotImplementedError(f"generate(num_beams=k) runs HIP kernels: the model and input_ids must live on a ROCm device (got {dev})")
+        G, P = input_ids.shape
+        B = G * k
+        if pad_token_id is None:
+            pad_token_id = getattr(self, "pad_token_id", None)
+        pad_token_id = 0 if pad_token_id is None else int(pad_token_id)
+        N = max(int(max_length) - P, 0)
+        fields = ["sequences", "scores", "sequences_scores"] + ["logprobs"] * bool(output_logprobs)
+        if N == 0:                                     # nothing to generate: every beam is the prompt
+            seq = input_ids.repeat_interleave(n, 0)
+            if not return_dict_in_generate:
+                return seq
+            values = [seq, None, torch.zeros(G * n, dtype=torch.float32, device=dev)] + [torch.empty(G * n, 0, device=dev)] * bool(output_logprobs)
+            return namedtuple("BeamSearchDecoderOnlyOutput", fields)(*values)
+        allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G, k, N, dev)
+        if V is not None:
+            check_masks(V, V if vocab_size is None else int(vocab_size))
+        ip = InferenceParams(max_seqlen=P + N, max_batch_size=B)
+        ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N, fan=k, prompt_len=P)
+        if ip.key_value_memory_dict is None:
+            raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
+        out = self(input_ids, inference_params=ip)
+        logits = out[0] if isinstance(out, tuple) else out
+        logits = logits.logits if hasattr(logits, "logits") else logits                            # (G, P, V)
+        if V is None:
+            V = logits.shape[-1]
+            if V > _lib.SAMPLE_MAX_V:
+                raise ValueError(f"generate(num_beams=k) serves logits of at most {_lib.SAMPLE_MAX_V} columns (this model has {V})")
+            if vocab_size is not None and not 1 <= int(vocab_size) <= V:
+                raise ValueError(f"vocab_size={vocab_size}: the logits have {V} columns")
+            check_masks(V, V if vocab_size is None else int(vocab_size))
+        last = logits[:, -1].repeat_interleave(k, 0)
+        search = BeamSearcher(ip.key_value_memory_dict.values(), input_ids, k, N, eos=eos_token_id, pad=pad_token_id, vocab=vocab_size, allow=allow)
+        ip.seqlen_offset = P
+        step = GraphedDecodeStep(self, ip, B, sampler=search) if cg and N > 1 else None
+        nxt = step.ids if step is not None else torch.empty(B, 1, dtype=torch.int64, device=dev)
+        try:
+            search(last, nxt)
+            n_done = 1
+            for i in range(1, N):
+                if stop_check_every and i % stop_check_every == 0 and bool(search.done.all()):
+                    break
+                if step is not None:
+                    step.replay()
+                else:
+                    search(_last_logits(self(nxt, inference_params=ip)), nxt)
+                ip.seqlen_offset += 1
+                n_done = i + 1
+        finally:
+            if step is not None:
+                step.release()
+        seq, scores, logprobs = search.finalize(n_done, n, want_logprobs=output_logprobs)
+        if not return_dict_in_generate:
+            return seq
+        return namedtuple("BeamSearchDecoderOnlyOutput", fields)(*([seq, None, scores] + [logprobs] * bool(output_logprobs)))
 
 
     def _generate_ragged(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
@@ -965,6 +1081,16 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         return {m._decode_key(): m.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, fan=fan, prompt_len=prompt_len,
                                                             lookahead=lookahead)
                 for m in self._mixers()}
+
+    def reorder_inference_cache(self, inference_params, parents):
+        """``_reorder_cache``: every layer's decode cache continues row b as what row ``parents[b]`` was (``HyenaDecodeState.reorder``:
+        device int32 (B,), parents within b's fan group; fan-out caches only).  Every layer is checked before any of them moves."""
+        states = list(inference_params.key_value_memory_dict.values())
+        for s in states:
+            if s.fan == 1 or s.ragged or s.W:
+                s.reorder(parents)                     # raises
+        for s in states:
+            s.reorder(parents)
 
     def forward(self, input_ids, position_ids=None, inference_params=None, state=None):
         # (the head through projection.hyena_linear: its weight gradient contracts 16 x 256 outputs over 10^6 tokens, which the GEMM library

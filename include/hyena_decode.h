@@ -181,6 +181,58 @@ int hyena_decode_sample_constrained(const void* logits, long ldl, int dtype, int
                                     int ncols, long long* next, long ldn, float* scores, float* u_out, const unsigned long long* allow,
                                     long lda, int nallow, const int* start, float* logprobs, long ldp, void* stream);
 
+/* Beam search over the fan-out layout: the k = `fan` beams of a prompt are the k rows of a fan group, row g k + r holding rank r of prompt
+ * g, best first.  1 <= k <= HYENA_DECODE_BEAM_MAX, B = G k rows, 1 <= Vlive <= V <= 64.
+ *
+ * hyena_decode_beam -- the beam step, in the sampler's place as the last node of a step: one 64-lane workgroup per group.  Group g stands at
+ * column c = col[g k] (one value per group); c outside [0, ncols): parked, nothing of the group is read or written.  Otherwise
+ *   1. log-probabilities.  For a live row j (done[j] == 0), lp[j][i] = (l_i - m) - log(sum_{v < Vlive} exp(l_v - m)), m the maximum of the
+ *      live logits (NaNs skipped): exactly the value hyena_decode_sample_constrained defines for its `logprobs` -- fp32, the sum serial in
+ *      index order, NaN where m or the sum is not finite.  The model's own distribution at temperature 1 over ALL live tokens, not
+ *      renormalised over the allowed set: a beam's score is the log-likelihood of its tokens under the model.
+ *   2. candidates.  A live row j contributes every token i of its allowed set A -- `allow`, `lda`, `nallow`, `start` and the rule that an
+ *      empty set means the whole live vocabulary as in hyena_decode_sample_constrained, n = c - start[row] -- with score
+ *      beam_score[j] + lp[j][i].  A finished row contributes exactly ONE candidate: token `pad`, its score unchanged (flat index j V).
+ *      Everything else is excluded.  Every row yields a candidate, so at least k exist.
+ *   3. selection.  The first k candidates in this order: numbers by score descending (-inf included), then NaN scores; ties -- equal
+ *      scores, two NaNs -- by the flat index j V + i ascending.  The order is total for every input.  Rank r goes to row g k + r.
+ *   4. writes for row b = g k + r: parent[b] = the ABSOLUTE row index of the candidate's row; beam_score[b] = its score; done[b] = the
+ *      parent's flag, or 1 if the token is `eos` (eos < 0: none); next[b ldn] = the token (`pad` for a finished row); col[b] = c + 1; and
+ *      the records tok_hist / parent_hist / lp_hist [b ldh + n] = token / parent / lp of the token (0 for a finished row's pad), n =
+ *      c - start[b], written only for n in [0, nrec) (each record may be NULL).  One lane writes, after every lane has read the group's
+ *      state; no atomics.
+ * The caller initialises beam_score to 0 for rank 0 and -inf for the other rows of every group: the first step's k identical rows then
+ * expand as one.  Bad arguments (a null required pointer -- everything but allow and the records --, fan outside [1, HYENA_DECODE_BEAM_MAX],
+ * B not a multiple of fan, V > 64, Vlive outside [1, V], an unknown dtype, ldl < V, ncols < 1, ldn < 1, nallow < 1 or 0 < lda < nallow
+ * with allow given, nrec < 1 or ldh < nrec with a record given) return HYENA_ERR_BAD_ARG before anything is launched.
+ *
+ * hyena_decode_reorder_fan -- re-parents the rows of ONE layer's fan-out cache in place (what a key-value cache calls _reorder_cache).  With
+ * t1 = *pos (the position hyena_decode_post_fan left) and c0 the first column that can differ between the rows of a group (the prompt
+ * length), S <= c0 <= Lcap:
+ *     vgr[b, d, s - S] = old vgr[parent[b], d, s - S]   for c0 <= s < t1, every d;      tail[c, b, :] = old tail[c, parent[b], :]   for c < 3 D
+ * for every row b < B.  A parent[b] outside b's own group is taken as b.  t1 outside [S, Lcap]: nothing is written.  The shared history,
+ * the columns below c0 and the columns from t1 on are never touched.  One thread owns one (group, channel, column) -- or (group, tail
+ * element) -- for all k rows, loads the k values through parent[] and only then stores them: no scratch, no second launch.  The grid
+ * depends on Lcap - c0, the live range on *pos: one captured launch serves every token.
+ * Bytes moved per layer and step: 2 B D (t1 - c0) sizeof(dtype) for the history (read + write) plus 48 B D for the tails -- linear in the
+ * number of tokens generated so far and independent of the prompt length.
+ * Bad arguments (everything hyena_decode_post_fan refuses for vgr / B / fan / D / Lcap / S / ldr / dtype, a null tail, parent or pos,
+ * fan > HYENA_DECODE_BEAM_MAX, Bcap < B, c0 outside [S, Lcap]) return HYENA_ERR_BAD_ARG before anything is launched.
+ *
+ * hyena_decode_beam_backtrack -- once after the last step, one thread per returned row q = g n_ret + r (1 <= n_ret <= fan): starting at row
+ * g k + r it walks the records from step n_done - 1 back to step 0: seq[q lds + P + i] = tok_hist[row, i], logprobs[q ldp + i] =
+ * lp_hist[row, i] (logprobs may be NULL), then row = parent_hist[row, i] (a parent outside [0, B) is taken as the row itself).
+ * 0 <= n_done <= ldh, lds >= P + n_done, ldp >= n_done; bad arguments return HYENA_ERR_BAD_ARG. */
+#define HYENA_DECODE_BEAM_MAX 16
+int hyena_decode_beam(const void* logits, long ldl, int dtype, int B, int fan, int V, int Vlive, int eos, int pad, int* col, int* done,
+                      float* beam_score, const int* start, int* parent, long long* next, long ldn, int ncols,
+                      const unsigned long long* allow, long lda, int nallow, int* tok_hist, int* parent_hist, float* lp_hist, long ldh,
+                      int nrec, void* stream);
+int hyena_decode_reorder_fan(void* vgr, float* tail, const int* parent, const int* pos, int B, int Bcap, int fan, int D, int Lcap, int S,
+                             int c0, int ldr, int dtype, void* stream);
+int hyena_decode_beam_backtrack(const int* tok_hist, const int* parent_hist, const float* lp_hist, long ldh, int B, int fan, int n_done,
+                                int n_ret, long long* seq, long lds, int P, float* logprobs, long ldp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
