@@ -227,6 +227,12 @@ def lib():
         L.hyena_decode_beam_backtrack.restype = c_int
         L.hyena_decode_beam_backtrack.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, c_void_p,
                                                   ctypes.c_long, c_int, c_void_p, ctypes.c_long, c_void_p]
+        # automaton-constrained generation: the sampler and the beam step with the mask from (state, new-token number) tables
+        auto_args = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]              # M, Nt, S, delta, Vdelta, dstate
+        L.hyena_decode_sample_automaton.restype = c_int
+        L.hyena_decode_sample_automaton.argtypes = L.hyena_decode_sample.argtypes[:-1] + auto_args + [c_void_p, c_void_p, ctypes.c_long, c_void_p]
+        L.hyena_decode_beam_automaton.restype = c_int
+        L.hyena_decode_beam_automaton.argtypes = L.hyena_decode_beam.argtypes[:17] + auto_args + L.hyena_decode_beam.argtypes[20:]
         # input projection on the matrix cores + front of the shell (include/hyena_proj.h)
         L.hyena_inproj_pre_fwd_ld.restype = c_int
         L.hyena_inproj_pre_fwd_ld.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -1156,10 +1162,22 @@ def decode_post_la(part, carry, hist, fb, x0, z, pos, base, B, Lcap):
 
 # ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------
 SAMPLE_MAX_V = 64
+AUTOMATON_MAX_STATES = 4096  # HYENA_DECODE_AUTOMATON_MAX_STATES: states of a token automaton
+AUTOMATON_MAX_TABLE = 1 << 22  # HYENA_DECODE_AUTOMATON_MAX_TABLE: entries Nt S of its step table M
+
+
+def _automaton_tables(automaton, B, V, dev):
+    """(M (Nt, S) int64, delta (S, V) int32, dstate (B,) int32), all contiguous on ``dev`` -> the six arguments of the C entry points"""
+    M, delta, dstate = automaton
+    assert M.dtype == torch.int64 and M.dim() == 2 and M.is_contiguous() and M.shape[0] >= 1
+    assert delta.dtype == torch.int32 and delta.dim() == 2 and delta.is_contiguous() and delta.shape[0] == M.shape[1]
+    assert dstate.dtype == torch.int32 and dstate.shape == (B,) and dstate.is_contiguous()
+    assert M.device == delta.device == dstate.device == dev
+    return M.data_ptr(), M.shape[0], M.shape[1], delta.data_ptr(), delta.shape[1], dstate.data_ptr()
 
 
 def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, top_p=1.0, eos=-1, pad=0, vocab=None, scores=None, u_out=None,
-                  allow=None, start=None, logprobs=None):
+                  allow=None, start=None, logprobs=None, automaton=None):
     """logits (B, V <= 64) fp32 / bf16 / fp16, rows contiguous -> row b's token at seq[b, col[b]] and nxt[b]; col advanced, done set on `eos`
     (< 0: none); a parked row (col outside seq's columns) is left alone, a done row only gets nxt[b] = pad.  ``seed``: device int64 (1,);
     ``col`` / ``done``: device int32 (B,); ``seq`` (B, ncols) and ``nxt`` (B,) or (B, 1): int64; ``vocab``: the live columns (default V);
@@ -1168,7 +1186,11 @@ def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, t
     ``allow`` / ``start`` / ``logprobs`` all None: hyena_decode_sample.  Otherwise hyena_decode_sample_constrained: ``start`` int32 (B,) the
     column of every row's first new token; ``allow`` int64 bit masks (N,) -- one row for the batch -- or (B, N), bit v of allow[b, i]: token
     v may be row b's i-th new token (an empty mask, or i outside [0, N): unconstrained); ``logprobs`` (B, N') fp32 receives at
-    [b, col[b] - start[b]] the emitted token's log-probability under the softmax of the live logits at temperature 1."""
+    [b, col[b] - start[b]] the emitted token's log-probability under the softmax of the live logits at temperature 1.
+
+    ``automaton`` = (M, delta, dstate): hyena_decode_sample_automaton -- row b's mask is M[n, dstate[b]] (M (Nt, S) int64; Nt == 1: M[0] for
+    every n), and dstate[b] (int32 (B,)) moves on to delta[dstate[b], token] (delta (S, V) int32, -1: forbidden).  Needs ``start``; not
+    together with ``allow`` (positional masks are folded into M)."""
     _require_gpu(logits, "logits")
     assert logits.dim() == 2 and logits.stride(1) == 1
     B, V = logits.shape
@@ -1182,6 +1204,20 @@ def decode_sample(logits, seed, col, done, seq, nxt, temperature=1.0, top_k=1, t
     assert u_out is None or (u_out.dtype == torch.float32 and u_out.shape == (B,) and u_out.is_contiguous())
     for t in (seed, col, done, seq, nxt, scores, u_out):
         assert t is None or t.device == logits.device
+    if automaton is not None:
+        assert allow is None and start is not None and start.dtype == torch.int32 and start.shape == (B,) and start.is_contiguous()
+        assert logprobs is None or (logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.shape[0] == B
+                                    and logprobs.shape[1] >= 1 and logprobs.is_contiguous())
+        assert start.device == logits.device and (logprobs is None or logprobs.device == logits.device)
+        with _backend.guard(logits.device):
+            check(lib().hyena_decode_sample_automaton(
+                logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, V, V if vocab is None else int(vocab),
+                float(temperature), int(top_k), float(top_p), seed.data_ptr(), int(eos), int(pad), col.data_ptr(), done.data_ptr(),
+                seq.data_ptr(), seq.stride(0) if B > 1 else ncols, ncols, nxt.data_ptr(), nxt.stride(0) if B > 1 else 1,
+                None if scores is None else scores.data_ptr(), None if u_out is None else u_out.data_ptr(),
+                *_automaton_tables(automaton, B, V, logits.device), start.data_ptr(), None if logprobs is None else logprobs.data_ptr(),
+                0 if logprobs is None else logprobs.shape[1], _backend.stream(logits.device)))
+        return
     if allow is not None or start is not None or logprobs is not None:
         assert start is not None and start.dtype == torch.int32 and start.shape == (B,) and start.is_contiguous()
         assert allow is None or (allow.dtype == torch.int64 and allow.dim() in (1, 2) and allow.shape[-1] >= 1 and allow.is_contiguous()
@@ -1219,13 +1255,15 @@ def _beam_rows(B, fan, *tensors):
 
 
 def decode_beam(logits, score, col, done, start, parent, nxt, fan, ncols, eos=-1, pad=0, vocab=None, allow=None, tok_hist=None, parent_hist=None,
-                lp_hist=None):
+                lp_hist=None, automaton=None):
     """The beam step: logits (B = G fan, V <= 64) fp32 / bf16 / fp16, rows contiguous; the ``fan`` rows of a group are the beams of one
     prompt, best first.  ``score`` fp32 (B,) cumulative log-probabilities (0 / -inf ... before the first step); ``col`` / ``done`` /
     ``start`` / ``parent``: device int32 (B,); ``nxt`` (B,) or (B, 1) int64.  Per group the ``fan`` best of {live row, allowed token} and
     {finished row, pad} by score (then NaN scores; ties by row, then token) go to its rows in rank order: ``parent`` (absolute row),
     ``score``, ``done``, ``nxt``, ``col`` + 1 and the records ``tok_hist`` / ``parent_hist`` (int32) / ``lp_hist`` (fp32), all (B, N'), at
-    [b, col[b] - start[b]].  A group whose column lies outside [0, ncols) is left alone.  ``allow``: as for ``decode_sample``."""
+    [b, col[b] - start[b]].  A group whose column lies outside [0, ncols) is left alone.  ``allow``: as for ``decode_sample``.
+    ``automaton`` = (M, delta, dstate), not together with ``allow``: hyena_decode_beam_automaton -- row b's allowed set is M[n, dstate[b]],
+    and rank r receives the state delta[dstate[parent], token] (its parent's as it is for pad and eos)."""
     _require_gpu(logits, "logits")
     assert logits.dim() == 2 and logits.stride(1) == 1
     B, V = logits.shape
@@ -1241,6 +1279,16 @@ def decode_beam(logits, score, col, done, start, parent, nxt, fan, ncols, eos=-1
     for t in [score, col, done, start, parent, nxt, allow] + recs:
         assert t is None or t.device == logits.device
     nrec = recs[0].shape[1] if recs else 0
+    if automaton is not None:
+        assert allow is None
+        with _backend.guard(logits.device):
+            check(lib().hyena_decode_beam_automaton(
+                logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, int(fan), V, V if vocab is None else int(vocab),
+                int(eos), int(pad), col.data_ptr(), done.data_ptr(), score.data_ptr(), start.data_ptr(), parent.data_ptr(), nxt.data_ptr(),
+                nxt.stride(0) if B > 1 else 1, int(ncols), *_automaton_tables(automaton, B, V, logits.device),
+                None if tok_hist is None else tok_hist.data_ptr(), None if parent_hist is None else parent_hist.data_ptr(),
+                None if lp_hist is None else lp_hist.data_ptr(), nrec, nrec, _backend.stream(logits.device)))
+        return
     with _backend.guard(logits.device):
         check(lib().hyena_decode_beam(
             logits.data_ptr(), logits.stride(0) if B > 1 else V, dtype_code(logits.dtype), B, int(fan), V, V if vocab is None else int(vocab),

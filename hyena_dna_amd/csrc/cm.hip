@@ -161,6 +161,15 @@ static_assert(DEC_TMAX == HYENA_DECODE_TMAX, "the header's block limit");
             default: HY_LAUNCH((kernel<DT_F16>), grid, dim3(threads), smem, stream, a); break;                        \
         }                                                                                                             \
     } while (0)
+// the automaton instantiation of a kernel template <DT, AUTO, Args> (decode_sample_con_kernel, decode_beam_kernel)
+#define HY_DEC_DISPATCH_AUTO(kernel, Args, grid, threads, smem)                                                      \
+    do {                                                                                                              \
+        switch (dtype) {                                                                                              \
+            case HYENA_F32: HY_LAUNCH((kernel<DT_F32, true, Args>), grid, dim3(threads), smem, stream, a); break;     \
+            case HYENA_BF16: HY_LAUNCH((kernel<DT_BF16, true, Args>), grid, dim3(threads), smem, stream, a); break;   \
+            default: HY_LAUNCH((kernel<DT_F16, true, Args>), grid, dim3(threads), smem, stream, a); break;            \
+        }                                                                                                             \
+    } while (0)
 }  // namespace
 
 extern "C" {
@@ -432,6 +441,34 @@ int hyena_decode_sample_constrained(const void* logits, long ldl, int dtype, int
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 
+// ---- automaton-constrained sampling (decode_sample_con_kernel, AUTO): the mask comes from M at the row's automaton state -------------------
+static bool dec_auto_ok(const unsigned long long* M, int Nt, int S, const int* delta, int Vdelta, const int* dstate, int V) {
+    return M != nullptr && delta != nullptr && dstate != nullptr && S >= 1 && S <= HYENA_DECODE_AUTOMATON_MAX_STATES && Nt >= 1 &&
+           (long)Nt * S <= HYENA_DECODE_AUTOMATON_MAX_TABLE && Vdelta == V;
+}
+
+int hyena_decode_sample_automaton(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
+                                  const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,
+                                  long long* next, long ldn, float* scores, float* u_out, const unsigned long long* M, int Nt, int S,
+                                  const int* delta, int Vdelta, int* dstate, const int* start, float* logprobs, long ldp, void* stream) {
+    if (logits == nullptr || seed == nullptr || col == nullptr || done == nullptr || seq == nullptr || next == nullptr || B < 1 || V < 1 ||
+        V > SMP_VMAX || Vlive < 1 || Vlive > V || !(top_p > 0.f && top_p <= 1.f) || !dec_dtype_ok(dtype) || ldl < V || ncols < 1 ||
+        lds < ncols || ldn < 1)
+        return HYENA_ERR_BAD_ARG;
+    if (start == nullptr || !dec_auto_ok(M, Nt, S, delta, Vdelta, dstate, V)) return HYENA_ERR_BAD_ARG;
+    if (logprobs != nullptr && ldp < 1) return HYENA_ERR_BAD_ARG;
+    SampleAutoArgs a;
+    a.logits = logits; a.scores = scores; a.u_out = u_out; a.seed = seed; a.col = col; a.done = done; a.seq = seq; a.next = next;
+    a.ldl = ldl; a.lds = lds; a.ldn = ldn;
+    a.B = B; a.V = V; a.Vlive = Vlive; a.ncols = ncols; a.top_k = top_k; a.eos = eos; a.pad = pad;
+    a.T = temperature > 1e-6f ? temperature : 1e-6f;
+    a.top_p = top_p;
+    a.allow = nullptr; a.start = start; a.logprobs = logprobs; a.lda = 0; a.ldp = ldp; a.nallow = 0;
+    a.t.dstate = dstate; a.t.M = M; a.t.delta = delta; a.t.S = S; a.t.Nt = Nt;
+    HY_DEC_DISPATCH_AUTO(decode_sample_con_kernel, SampleAutoArgs, dim3(B < SMP_MAX_GRID ? B : SMP_MAX_GRID), SMP_VMAX, SMP_CON_LDS_BYTES);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
 // ---- beam search (decode_beam_kernel, decode_reorder_fan_kernel, decode_beam_backtrack_kernel) ---------------------------------------------
 static_assert(BEAM_MAX == HYENA_DECODE_BEAM_MAX, "the header's beam limit");
 
@@ -454,6 +491,30 @@ int hyena_decode_beam(const void* logits, long ldl, int dtype, int B, int fan, i
     a.nallow = allow != nullptr ? nallow : 0; a.nrec = rec ? nrec : 0;
     const int G = B / fan;
     HY_DEC_DISPATCH(decode_beam_kernel, dim3(G < SMP_MAX_GRID ? G : SMP_MAX_GRID), SMP_VMAX, BEAM_LDS_BYTES);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+// ---- the beam step with the rows' allowed sets from an automaton (decode_beam_kernel, AUTO) ----------------------------------------------
+int hyena_decode_beam_automaton(const void* logits, long ldl, int dtype, int B, int fan, int V, int Vlive, int eos, int pad, int* col,
+                                int* done, float* beam_score, const int* start, int* parent, long long* next, long ldn, int ncols,
+                                const unsigned long long* M, int Nt, int S, const int* delta, int Vdelta, int* dstate, int* tok_hist,
+                                int* parent_hist, float* lp_hist, long ldh, int nrec, void* stream) {
+    if (logits == nullptr || col == nullptr || done == nullptr || beam_score == nullptr || start == nullptr || parent == nullptr ||
+        next == nullptr || B < 1 || fan < 1 || fan > BEAM_MAX || B % fan != 0 || V < 1 || V > SMP_VMAX || Vlive < 1 || Vlive > V ||
+        !dec_dtype_ok(dtype) || ldl < V || ncols < 1 || ldn < 1)
+        return HYENA_ERR_BAD_ARG;
+    if (!dec_auto_ok(M, Nt, S, delta, Vdelta, dstate, V)) return HYENA_ERR_BAD_ARG;
+    const bool rec = tok_hist != nullptr || parent_hist != nullptr || lp_hist != nullptr;
+    if (rec && (nrec < 1 || ldh < nrec)) return HYENA_ERR_BAD_ARG;
+    BeamAutoArgs a;
+    a.logits = logits; a.score = beam_score; a.col = col; a.done = done; a.start = start; a.parent = parent; a.next = next;
+    a.allow = nullptr; a.tok_hist = tok_hist; a.parent_hist = parent_hist; a.lp_hist = lp_hist;
+    a.ldl = ldl; a.ldn = ldn; a.lda = 0; a.ldh = ldh;
+    a.B = B; a.fan = fan; a.V = V; a.Vlive = Vlive; a.ncols = ncols; a.eos = eos; a.pad = pad;
+    a.nallow = 0; a.nrec = rec ? nrec : 0;
+    a.t.dstate = dstate; a.t.M = M; a.t.delta = delta; a.t.S = S; a.t.Nt = Nt;
+    const int G = B / fan;
+    HY_DEC_DISPATCH_AUTO(decode_beam_kernel, BeamAutoArgs, dim3(G < SMP_MAX_GRID ? G : SMP_MAX_GRID), SMP_VMAX, BEAM_AUTO_LDS_BYTES);
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 

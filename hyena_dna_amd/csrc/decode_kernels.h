@@ -972,9 +972,16 @@ enum { SMP_CON_LDS_BYTES = 5 * SMP_VMAX * 4 };
         m = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |                     \
             (unsigned)__builtin_amdgcn_readfirstlane((int)m);                                                          \
     } while (0)
+#define SMP_UNIFORM_ISSUED4(x, y, z, w)                                                                                \
+    do {                                                                                                               \
+        asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(w));                                                       \
+        x = __builtin_amdgcn_readfirstlane(x); y = __builtin_amdgcn_readfirstlane(y); z = __builtin_amdgcn_readfirstlane(z); \
+        w = __builtin_amdgcn_readfirstlane(w);                                                                         \
+    } while (0)
 #else
 #define SMP_UNIFORM_ISSUED3(x, y, z) ((void)0)
 #define SMP_ISSUED2_UNIFORM64(x, m) ((void)0)
+#define SMP_UNIFORM_ISSUED4(x, y, z, w) ((void)0)
 #endif
 
 struct SampleConArgs : SampleArgs {
@@ -985,8 +992,22 @@ struct SampleConArgs : SampleArgs {
     int nallow;
 };
 
-template <int DT>
-__global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConArgs a) {
+// The automaton tables of hyena_decode_sample_automaton / hyena_decode_beam_automaton (the semantics stand below decode_sample_con_kernel)
+struct AutoTabs {
+    int* dstate;                      // (B,) the automaton state of row b
+    const unsigned long long* M;      // (Nt, S) allowed sets by (new-token number, state); Nt == 1: one row for every number
+    const int* delta;                 // (S, V) the state after token v in state s; -1: forbidden
+    int S, Nt;
+};
+
+struct SampleAutoArgs : SampleConArgs {   // hyena_decode_sample_automaton (the semantics stand below the kernel)
+    AutoTabs t;
+};
+
+// AUTO = false, Args = SampleConArgs: the kernel of hyena_decode_sample_constrained, as it has always been (every `if constexpr (AUTO)` is
+// discarded); AUTO = true, Args = SampleAutoArgs: the same body with the mask from the automaton's tables
+template <int DT, bool AUTO = false, class Args = SampleConArgs>
+__global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(Args a) {
     typedef typename Elem<DT>::type elem_t;
     HY_SMEM(smem);
     HY_LDS float* sl = HY_LDS_CAST(float, smem);                 // [64] live logits by index
@@ -1008,15 +1029,28 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConAr
         int c = a.col[b];
         int fin = a.done[b];
         int c0 = first_col[b];
-        SMP_UNIFORM_ISSUED3(c, fin, c0);
+        int st = 0;                                              // AUTO: the row's state, out with col, done and start -- still two trips
+        if constexpr (AUTO) {
+            st = a.t.dstate[b];
+            SMP_UNIFORM_ISSUED4(c, fin, c0, st);
+        } else {
+            SMP_UNIFORM_ISSUED3(c, fin, c0);
+        }
         if (c < 0 || c >= a.ncols) continue;                     // parked
         if (fin != 0) {
             if (i == 0) a.next[(size_t)b * a.ldn] = a.pad;
             continue;
         }
         const long n = (long)c - c0;
-        const bool masked = a.allow != nullptr && n >= 0 && n < a.nallow;
-        const unsigned long long* mp = masked ? a.allow + ((size_t)b * a.lda + n) : a.seed;
+        bool masked;
+        const unsigned long long* mp;
+        if constexpr (AUTO) {                                    // (a state outside the table: the row samples unmasked and keeps it)
+            masked = st >= 0 && st < a.t.S && (a.t.Nt == 1 || (n >= 0 && n < a.t.Nt));
+            mp = masked ? a.t.M + ((size_t)(a.t.Nt == 1 ? 0 : n) * a.t.S + st) : a.seed;
+        } else {
+            masked = a.allow != nullptr && n >= 0 && n < a.nallow;
+            mp = masked ? a.allow + ((size_t)b * a.lda + n) : a.seed;
+        }
         float l = Elem<DT>::dec(reinterpret_cast<const elem_t*>(a.logits)[(size_t)b * a.ldl + (i < a.V ? i : 0)]);
         unsigned long long m = mp[0];
         SMP_ISSUED2_UNIFORM64(l, m);
@@ -1089,6 +1123,9 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConAr
             if (i == 0 && a.u_out != nullptr) a.u_out[b] = u;
         }
         if (i == 0) {
+            int ns = -1;                                         // AUTO: the one load of delta, at the tail, in front of the stores
+            if constexpr (AUTO)
+                if (st >= 0 && st < a.t.S) ns = a.t.delta[(size_t)st * a.V + tok];
             a.seq[(size_t)b * a.lds + c] = tok;
             a.next[(size_t)b * a.ldn] = tok;
             a.col[b] = c + 1;
@@ -1097,9 +1134,23 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_sample_con_kernel(SampleConAr
                 const bool ok = lmax - lmax == 0.f && lsum - lsum == 0.f;
                 a.logprobs[(size_t)b * a.ldp + n] = ok ? (ltok - lmax) - logf(lsum) : __builtin_nanf("");
             }
+            if constexpr (AUTO)
+                if (ns >= 0 && tok != a.eos) a.t.dstate[b] = ns;   // (eos, or a forbidden token out of the total fall-back: the state stays)
         }
     }
 }
+
+// ---- automaton-constrained sampling (C ABI: hyena_decode_sample_automaton) -----------------------------------------------------------------
+// decode_sample_con_kernel with the row's mask looked up by the state of a deterministic automaton that the row carries in device memory:
+// with s = dstate[b] and n = c - start[b], the mask is M[(Nt == 1 ? 0 : n) S + s] -- M (Nt, S) holds, for every new-token number and state,
+// the tokens after which an accepted word can still be completed (the host computes it backwards; Nt == 1: the same row for every n).
+// Everything from the mask on is decode_sample_con_kernel operation for operation (one body, a template parameter apart): A, ranks, greedy,
+// top-k, top-p, the Philox word of (seed, row, column), the log-prob over all live tokens, and the rule that a mask without a bit below
+// Vlive means the whole live vocabulary.  After the token is chosen lane 0 writes dstate[b] = delta[s V + tok].  The state stays as it is
+// for a finished row, for a row that has just emitted eos, for a -1 transition (reachable through the total fall-back only) and for an s
+// outside [0, S) -- such a row, and one with Nt > 1 and n outside [0, Nt), also samples unmasked.  Parked rows touch nothing.
+// Loads: dstate[b] goes out with col, done and start, the mask with the row's logits -- two dependent trips as before; delta is read by
+// lane 0 at the tail, in front of the stores.  s, like c, is one address for the wavefront: the branches around barriers stay uniform.
 
 // ---- beam search: the beam step, the cache reorder, the backtrack (C ABI: hyena_decode_beam, _reorder_fan, _beam_backtrack) ------------------
 // The k beams of a prompt are the k = `fan` rows of a fan group (row g k + r: rank r of prompt g, best first).  The beam step takes the
@@ -1151,8 +1202,14 @@ __device__ __forceinline__ bool beam_before(float sa, int ia, float sb, int ib) 
 __device__ __forceinline__ uint32_t beam_f32_bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, 4); return u; }
 __device__ __forceinline__ float beam_bits_f32(uint32_t u) { float v; __builtin_memcpy(&v, &u, 4); return v; }
 
-template <int DT>
-__global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
+struct BeamAutoArgs : BeamArgs {           // hyena_decode_beam_automaton (the semantics stand below the kernel)
+    AutoTabs t;
+};
+
+// AUTO = false, Args = BeamArgs: the kernel of hyena_decode_beam, as it has always been (every `if constexpr (AUTO)` is discarded);
+// AUTO = true, Args = BeamAutoArgs: the same body with the rows' allowed sets from the automaton's tables
+template <int DT, bool AUTO = false, class Args = BeamArgs>
+__global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(Args a) {
     typedef typename Elem<DT>::type elem_t;
     HY_SMEM(smem);
     HY_LDS float* sl = HY_LDS_CAST(float, smem);                 // [k][BEAM_LD] live logits by (row, index); then the candidates' scores
@@ -1168,6 +1225,8 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
     HY_LDS float* ssc = HY_LDS_CAST(float, rd + BEAM_MAX);       // [k] beam_score of row j
     HY_LDS int* sAlo = rd + 2 * BEAM_MAX;                        // [k] allowed set of row j, low and high word
     HY_LDS int* sAhi = sAlo + BEAM_MAX;
+    [[maybe_unused]] HY_LDS int* sst = sAhi + BEAM_MAX;          // [k] AUTO: automaton state of row j
+    [[maybe_unused]] HY_LDS int* rst = sst + BEAM_MAX;           // [k] AUTO: result: state of rank r
     const int i = threadIdx.x, k = a.fan;
     const float ninf = -__builtin_inff();
     const unsigned long long all = a.Vlive >= 64 ? ~0ull : (1ull << a.Vlive) - 1ull;
@@ -1190,9 +1249,18 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
             sc_row = a.score[b0 + i];
             fin_row = a.done[b0 + i];
             const long n = (long)c - a.start[b0 + i];
-            if (a.allow != nullptr && n >= 0 && n < a.nallow) {
-                const unsigned long long m = a.allow[(size_t)(b0 + i) * a.lda + n] & all;
-                if (m != 0ull) A_row = m;
+            if constexpr (AUTO) {
+                const int st = a.t.dstate[b0 + i];
+                if (st >= 0 && st < a.t.S && (a.t.Nt == 1 || (n >= 0 && n < a.t.Nt))) {
+                    const unsigned long long m = a.t.M[(size_t)(a.t.Nt == 1 ? 0 : n) * a.t.S + st] & all;
+                    if (m != 0ull) A_row = m;
+                }
+                sst[i] = st;
+            } else {
+                if (a.allow != nullptr && n >= 0 && n < a.nallow) {
+                    const unsigned long long m = a.allow[(size_t)(b0 + i) * a.lda + n] & all;
+                    if (m != 0ull) A_row = m;
+                }
             }
             sfin[i] = fin_row;
             ssc[i] = sc_row;
@@ -1266,11 +1334,25 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
                 rd[r] = (sfin[pj] != 0 || (!fin && tok == a.eos)) ? 1 : 0;
             }
         }
+        if constexpr (AUTO) {                                    // lane r: the state of rank r, out of its parent's (read before any write)
+            __syncthreads();
+            if (i < k) {
+                const int pj = rp[i], tok = rt[i], ps = sst[pj];
+                int ns = ps;                                     // a finished beam's pad, an eos, a state outside the table: the parent's state
+                if (sfin[pj] == 0 && tok != a.eos && ps >= 0 && ps < a.t.S) {
+                    const int d = a.t.delta[(size_t)ps * a.V + tok];
+                    if (d >= 0) ns = d;                          // (-1: through the total fall-back only)
+                }
+                rst[i] = ns;
+            }
+            __syncthreads();
+        }
         // (lane 0 wrote the results itself; every lane's reads of score / done / start / col lie before the barriers above)
         if (i == 0) {
             for (int r = 0; r < k; ++r) {
                 const long b = b0 + r;
                 const long n = (long)c - a.start[b];
+                if constexpr (AUTO) a.t.dstate[b] = rst[r];
                 a.parent[b] = (int)(b0 + rp[r]);
                 a.score[b] = rs[r];
                 a.done[b] = rd[r];
@@ -1285,6 +1367,15 @@ __global__ void __launch_bounds__(SMP_VMAX) decode_beam_kernel(BeamArgs a) {
         }
     }
 }
+
+// ---- automaton-constrained beam step (C ABI: hyena_decode_beam_automaton) -------------------------------------------------------------------
+// decode_beam_kernel with row j's allowed set looked up as the automaton sampler looks it up: lane j < k loads dstate[b0 + j] and
+// M[(Nt == 1 ? 0 : n) S + state] with the row's score and done flag, and keeps the state in LDS with the other per-row state -- all k are
+// read before any row of the group is written.  The order, the selection rounds and the records are decode_beam_kernel's (one body).  After
+// the rounds lane r takes rank r's state out of its parent's: delta[state[parent] V + tok]; the parent's own state for a finished beam's
+// pad candidate, for eos, for a -1 transition and for a state outside [0, S) (whose row had the whole live vocabulary).  Lane 0 writes it
+// with the rest: the state travels inside the beam kernel, decode_reorder_fan_kernel never sees it.
+enum { BEAM_AUTO_LDS_BYTES = BEAM_LDS_BYTES + 2 * BEAM_MAX * 4 };
 
 // Re-parenting the rows of one layer's fan-out cache in place: with t1 = *pos (the position decode_post_fan left) and c0 the first column
 // that can differ between the rows of a group (the prompt length),

@@ -15,7 +15,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable", "check_lookahead", "token_mask", "iupac_constraints"]
+__all__ = ["InferenceParams", "HyenaDecodeState", "DeviceSampler", "check_decodable", "check_lookahead", "token_mask", "iupac_constraints",
+           "TokenAutomaton", "motif_automaton", "automaton_step_tables"]
 
 
 class InferenceParams:
@@ -343,11 +344,14 @@ class DeviceSampler:
     captured graph may end with the call (``GraphedDecodeStep(..., sampler=...)``)."""
 
     def __init__(self, seq, col, seed, temperature=1.0, top_k=1, top_p=1.0, eos=None, pad=0, vocab=None, want_scores=False, V=None, allow=None,
-                 want_logprobs=False, n_new=None):
+                 want_logprobs=False, n_new=None, automaton_tables=None):
         """``allow``: int64 bit masks, (N,) for every row or (B, N): bit v of allow[b, i] lets token v be row b's i-th new token, counted
         from ``col`` as it stands now (``token_mask``, ``iupac_constraints``).  ``want_logprobs``: ``logprobs`` (B, ``n_new``; default ncols) fp32 receives at
         [b, i] the log-probability of row b's i-th new token under the softmax of its live logits at temperature 1 (NaN where none was
-        written).  Either one selects hyena_decode_sample_constrained; with neither the sampler runs hyena_decode_sample as before."""
+        written).  Either one selects hyena_decode_sample_constrained; with neither the sampler runs hyena_decode_sample as before.
+        ``automaton_tables`` = (M (Nt, S) int64, delta (S, V) int32, dstate (B,) int32) on the device, instead of ``allow``:
+        hyena_decode_sample_automaton -- row b's mask is M[i, dstate[b]] and ``dstate``, which the sampler owns from here on, follows
+        ``delta`` (``automaton_step_tables``; 8 Nt S + 4 S V + 4 B bytes)."""
         dev = seq.device
         self.seq, self.col = seq, col
         self.done = torch.zeros_like(col)
@@ -356,7 +360,11 @@ class DeviceSampler:
         self.eos, self.pad, self.vocab = (-1 if eos is None else int(eos)), int(pad), vocab
         self.scores = torch.zeros(seq.shape[0], seq.shape[1], V, dtype=torch.float32, device=dev) if want_scores else None
         self.allow = allow
-        self.start = col.clone() if allow is not None or want_logprobs else None
+        self.automaton = automaton_tables
+        if automaton_tables is not None and allow is not None:
+            raise ValueError("a sampler with automaton_tables takes its positional masks inside M: allow must be None")
+        self.dstate = None if automaton_tables is None else automaton_tables[2]
+        self.start = col.clone() if allow is not None or want_logprobs or automaton_tables is not None else None
         self.logprobs = None
         if want_logprobs:
             self.logprobs = torch.full((seq.shape[0], max(int(seq.shape[1] if n_new is None else n_new), 1)), float("nan"), dtype=torch.float32,
@@ -365,14 +373,15 @@ class DeviceSampler:
     def __call__(self, logits, nxt):
         _lib.decode_sample(logits, self.seed, self.col, self.done, self.seq, nxt, temperature=self.temperature, top_k=self.top_k,
                            top_p=self.top_p, eos=self.eos, pad=self.pad, vocab=self.vocab, scores=self.scores, allow=self.allow,
-                           start=self.start, logprobs=self.logprobs)
+                           start=self.start, logprobs=self.logprobs, **({} if self.automaton is None else dict(automaton=self.automaton)))
 
     def snapshot(self, steps):
-        """what up to ``steps`` calls from here may change -- col, done, the columns col[b] ... col[b] + steps - 1 of seq (and of scores),
-        the slots col[b] - start[b] ... + steps - 1 of logprobs -- as a function that puts it back (``GraphedDecodeStep``'s warm-up steps
-        run the real kernel)"""
+        """what up to ``steps`` calls from here may change -- col, done, the automaton states, the columns col[b] ... col[b] + steps - 1 of
+        seq (and of scores), the slots col[b] - start[b] ... + steps - 1 of logprobs -- as a function that puts it back
+        (``GraphedDecodeStep``'s warm-up steps run the real kernel)"""
         ncols = self.seq.shape[1]
         col, done = self.col.clone(), self.done.clone()
+        dstate = None if self.dstate is None else self.dstate.clone()
         idx = (col.to(torch.int64)[:, None] + torch.arange(int(steps), device=col.device)).clamp_(0, ncols - 1)      # (B, steps)
         seq = self.seq.gather(1, idx)
         sidx = None if self.scores is None else idx[:, :, None].expand(-1, -1, self.scores.shape[2])
@@ -383,6 +392,8 @@ class DeviceSampler:
         def restore():
             self.col.copy_(col)
             self.done.copy_(done)
+            if dstate is not None:
+                self.dstate.copy_(dstate)
             self.seq.scatter_(1, idx, seq)
             if scores is not None:
                 self.scores.scatter_(1, sidx, scores)
@@ -403,7 +414,7 @@ class BeamSearcher:
     log-probability, 0 / -inf before the first call so that the k identical rows expand as one), ``done``, ``col``, ``parent`` (the last
     step's parents) and the records ``tok_hist`` / ``parent_hist`` / ``lp_hist`` (G k, n_new), which ``finalize`` reads backwards."""
 
-    def __init__(self, states, prompts, k, n_new, eos=None, pad=0, vocab=None, allow=None):
+    def __init__(self, states, prompts, k, n_new, eos=None, pad=0, vocab=None, allow=None, automaton_tables=None):
         self.states = list(states)
         self.prompts = prompts                                   # (G, P) int64
         G, P = prompts.shape
@@ -416,6 +427,11 @@ class BeamSearcher:
                 raise ValueError(f"the decode caches must be built with fan = {self.k} for {G} prompts of {P} positions")
         B = G * self.k
         self.eos, self.pad, self.vocab, self.allow = (-1 if eos is None else int(eos)), int(pad), vocab, allow
+        # (M, delta, dstate) as for DeviceSampler: hyena_decode_beam_automaton -- the state of a beam travels with it inside the beam kernel
+        self.automaton = automaton_tables
+        if automaton_tables is not None and allow is not None:
+            raise ValueError("a searcher with automaton_tables takes its positional masks inside M: allow must be None")
+        self.dstate = None if automaton_tables is None else automaton_tables[2]
         self.col = torch.full((B,), P, dtype=torch.int32, device=dev)
         self.start = self.col.clone()
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -432,7 +448,7 @@ class BeamSearcher:
     def __call__(self, logits, nxt):
         _lib.decode_beam(logits, self.score, self.col, self.done, self.start, self.parent, nxt, self.k, self.P + self.N, eos=self.eos,
                          pad=self.pad, vocab=self.vocab, allow=self.allow, tok_hist=self.tok_hist, parent_hist=self.parent_hist,
-                         lp_hist=self.lp_hist)
+                         lp_hist=self.lp_hist, **({} if self.automaton is None else dict(automaton=self.automaton)))
         for s in self.states:
             s.reorder(self.parent)
         self.calls += 1
@@ -441,7 +457,8 @@ class BeamSearcher:
         """what up to ``steps`` calls from here may change, as a function that puts it back (``GraphedDecodeStep``'s warm-up steps run the
         real kernels): the searcher's own state and, for every layer, the history columns [P, P + calls so far + steps) that the warm-up's
         reorders permute (``GraphedDecodeStep`` restores ``tail`` and ``pos`` itself, before it calls this)"""
-        own = [(t, t.clone()) for t in (self.score, self.col, self.done, self.parent, self.tok_hist, self.parent_hist, self.lp_hist)]
+        own = [(t, t.clone()) for t in (self.score, self.col, self.done, self.parent, self.tok_hist, self.parent_hist, self.lp_hist, self.dstate)
+               if t is not None]
         calls = self.calls
         hist = []
         for s in self.states:
@@ -504,3 +521,220 @@ def iupac_constraints(pattern, token_of=None):
         else:
             raise ValueError(f"pattern[{i}] = {ch!r}: an IUPAC nucleotide code ({' '.join(IUPAC)}) or '.'")
     return torch.tensor(out, dtype=torch.int64)
+
+
+# ---- token automata: constraints on what a row contains, not on where ------------------------------------------------------------------------
+# Pure host code up to the tables the kernels read (hyena_decode_sample_automaton, hyena_decode_beam_automaton in include/hyena_decode.h).
+IUPAC_COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A", "R": "Y", "Y": "R", "S": "S", "W": "W", "K": "M", "M": "K", "B": "V", "V": "B",
+                    "D": "H", "H": "D", "N": "N"}
+
+
+class TokenAutomaton:
+    """A deterministic automaton over the token alphabet, for ``generate(automaton=...)``: every returned row spells a word it accepts.
+
+    ``delta`` (S, V) int32: ``delta[s, v]`` is the state after token v in state s, -1 where v is forbidden there; V is the number of logit
+    columns (at most 64), 1 <= S <= 4096.  ``accept`` (S,) bool: the states a finished row may stand in (default: all).  ``start``: the state
+    before the first token.  ``context``: how many trailing prompt tokens the automaton reads, from ``start``, before the first new token
+    (a forbidden transition inside the prompt restarts it from ``start``).  The tensors are kept on the CPU."""
+
+    def __init__(self, delta, accept=None, start=0, context=0):
+        if not torch.is_tensor(delta) or delta.dim() != 2 or delta.dtype != torch.int32:
+            what = f"{tuple(delta.shape)} {delta.dtype}" if torch.is_tensor(delta) else type(delta).__name__
+            raise ValueError(f"delta must be an (S, V) int32 tensor (got {what})")
+        S, V = delta.shape
+        if not 1 <= S <= _lib.AUTOMATON_MAX_STATES:
+            raise ValueError(f"an automaton has 1 ... {_lib.AUTOMATON_MAX_STATES} states (delta has {S} rows)")
+        if not 1 <= V <= _lib.SAMPLE_MAX_V:
+            raise ValueError(f"an automaton reads 1 ... {_lib.SAMPLE_MAX_V} tokens, one per logit column (delta has {V} columns)")
+        delta = delta.detach().cpu().contiguous()
+        if int(delta.min()) < -1 or int(delta.max()) >= S:
+            raise ValueError(f"delta holds states in [0, {S}) and -1 for a forbidden token (got {int(delta.min())} ... {int(delta.max())})")
+        if accept is None:
+            accept = torch.ones(S, dtype=torch.bool)
+        if not torch.is_tensor(accept) or accept.shape != (S,) or accept.dtype != torch.bool:
+            what = f"{tuple(accept.shape)} {accept.dtype}" if torch.is_tensor(accept) else type(accept).__name__
+            raise ValueError(f"accept must be a ({S},) bool tensor (got {what})")
+        if not 0 <= int(start) < S:
+            raise ValueError(f"start={start}: a state in [0, {S})")
+        if int(context) < 0:
+            raise ValueError(f"context={context}: a number of prompt tokens")
+        self.delta, self.accept, self.start, self.context = delta, accept.detach().cpu().contiguous(), int(start), int(context)
+        self.S, self.V = S, V
+
+    def walk(self, tokens, state=None):
+        """the states after every token of ``tokens`` from ``state`` (default ``start``) -> list of ints; -1 from a forbidden token on"""
+        s = self.start if state is None else int(state)
+        out = []
+        for v in tokens:
+            v = int(v)
+            s = int(self.delta[s, v]) if s >= 0 and 0 <= v < self.V else -1
+            out.append(s)
+        return out
+
+    def accepts(self, tokens, state=None):
+        """no forbidden transition on the way and an accepting state at the end"""
+        s = ([self.start if state is None else int(state)] + self.walk(tokens, state))[-1]
+        return s >= 0 and bool(self.accept[s])
+
+    def initial_state(self, prompt):
+        """the state before the first new token: the automaton run from ``start`` over the last ``min(context, len(prompt))`` tokens of
+        ``prompt``; a forbidden transition on the way restarts it from ``start``"""
+        s = self.start
+        tail = list(prompt)[len(prompt) - min(self.context, len(prompt)):]
+        for v in tail:
+            v = int(v)
+            t = int(self.delta[s, v]) if 0 <= v < self.V else -1
+            s = self.start if t < 0 else t
+        return s
+
+
+def motif_automaton(avoid=(), require=(), max_homopolymer=None, reverse_complement=False, token_of=None, n_tokens=16):
+    """The automaton of a DNA designer's content constraints -> ``TokenAutomaton`` over ``n_tokens`` tokens.
+
+    ``avoid`` / ``require``: IUPAC strings (``IUPAC``; ``token_of`` as for ``iupac_constraints``).  No transition may complete an occurrence of
+    an avoided motif; every required motif must occur (one "seen" bit per listed motif; ``accept``: all seen).  ``reverse_complement=True``
+    adds the reverse complement of every motif: an avoided motif is avoided on both strands, a required one counts on either.
+    ``max_homopolymer=h``: no run of h + 1 equal bases.  A token that is not one of the four bases breaks every motif and every run (it keeps
+    the seen bits).  Built by subset construction over sets of (motif, prefix length), so an IUPAC class costs no expansion; not minimised.
+    ``context`` = the longest motif - 1, or h if that is larger.  More than 4096 states: ValueError."""
+    if token_of is None:
+        from .tokenizer import DNACharTokenizerLUT
+        token_of = DNACharTokenizerLUT().vocab
+    V = int(n_tokens)
+    if not 1 <= V <= _lib.SAMPLE_MAX_V:
+        raise ValueError(f"n_tokens={n_tokens}: 1 ... {_lib.SAMPLE_MAX_V} logit columns")
+    bases = "ACGT"
+    ids = [int(token_of[b]) for b in bases]
+    if len(set(ids)) != 4 or not all(0 <= v < V for v in ids):
+        raise ValueError(f"token_of maps A C G T to {ids}: four different ids below n_tokens = {V}")
+    h = None if max_homopolymer is None else int(max_homopolymer)
+    if h is not None and h < 1:
+        raise ValueError(f"max_homopolymer={max_homopolymer}: at least 1")
+
+    def classes(motif, what):
+        motif = str(motif).upper()
+        if not motif or any(ch not in IUPAC for ch in motif):
+            raise ValueError(f"{what} motif {motif!r}: a non-empty string of IUPAC nucleotide codes ({' '.join(IUPAC)})")
+        out = [motif]
+        if reverse_complement:
+            rc = "".join(IUPAC_COMPLEMENT[ch] for ch in reversed(motif))
+            if rc != motif:
+                out.append(rc)
+        return [[frozenset(bases.index(b) for b in IUPAC[ch]) for ch in m] for m in out]
+
+    motifs = []                                                  # (classes per position, seen bit or None for an avoided motif)
+    for m in avoid:
+        motifs += [(c, None) for c in classes(m, "avoid")]
+    n_req = 0
+    for m in require:
+        motifs += [(c, n_req) for c in classes(m, "require")]
+        n_req += 1
+    all_seen = (1 << n_req) - 1
+    limit = _lib.AUTOMATON_MAX_STATES
+
+    def step(state, b):
+        """state (partial matches, last base, run, seen) after base b (0 .. 3) -> state, or None: forbidden"""
+        part, last, run, seen = state
+        if h is not None:
+            run = run + 1 if b == last else 1
+            last = b
+            if run > h:
+                return None
+        nxt = set()
+        for mi, p in list(part) + [(mi, 0) for mi in range(len(motifs))]:
+            cls, bit = motifs[mi]
+            if b in cls[p]:
+                if p + 1 == len(cls):
+                    if bit is None:
+                        return None
+                    seen |= 1 << bit
+                else:
+                    nxt.add((mi, p + 1))
+        return (frozenset(nxt), last, run, seen)
+
+    first = (frozenset(), -1, 0, 0)
+    index, order, rows = {first: 0}, [first], []
+    while len(rows) < len(order):
+        state = order[len(rows)]
+        row = []
+        for b in range(4):
+            t = step(state, b)
+            if t is not None and t not in index:
+                if len(order) >= limit:
+                    raise ValueError(f"these motifs need more than {limit} automaton states (the limit of a token automaton)")
+                index[t] = len(order)
+                order.append(t)
+            row.append(-1 if t is None else index[t])
+        t = (frozenset(), -1, 0, state[3])                      # any other token: no prefix, no run, the seen bits kept
+        if t not in index:
+            if len(order) >= limit:
+                raise ValueError(f"these motifs need more than {limit} automaton states (the limit of a token automaton)")
+            index[t] = len(order)
+            order.append(t)
+        row.append(index[t])
+        rows.append(row)
+    S = len(order)
+    delta = torch.empty(S, V, dtype=torch.int32)
+    table = torch.tensor(rows, dtype=torch.int32)               # (S, 5): A C G T, other
+    delta[:] = table[:, 4:5]
+    for b, v in enumerate(ids):
+        delta[:, v] = table[:, b]
+    accept = torch.tensor([st[3] == all_seen for st in order], dtype=torch.bool)
+    longest = max([len(c) for c, _ in motifs], default=1)
+    return TokenAutomaton(delta, accept, start=0, context=max(longest - 1, h or 0))
+
+
+def _mask_ints(bits):
+    """bool (..., V <= 64) -> int64 (...) with bit v set where bits[..., v] (bit 63 is the sign)"""
+    V = bits.shape[-1]
+    w = torch.tensor([(1 << v) - (1 << 64 if v == 63 else 0) for v in range(V)], dtype=torch.int64)
+    return (bits.to(torch.int64) * w).sum(-1)
+
+
+def automaton_step_tables(automaton, N, masks=None, eos=None, vocab=None, positional=None):
+    """The step table of N new tokens -> ``M`` (Nt, S) int64 on the CPU: bit v of M[i, s] says that token v may be the i-th new token in
+    state s, i.e. that an accepted word can still be completed after it.  Backwards from the end:
+        live[N][s] = accept[s]
+        M[i][s]    = { v != eos : v in P_i, delta[s, v] >= 0, live[i + 1][delta[s, v]] }  u  { eos : eos in P_i, accept[s] }
+        live[i][s] = M[i][s] is not empty
+    ``masks``: the positional sets P_i as (N,) int64 bit masks (None: every token), already without eos where ``min_new_tokens`` holds it
+    back; ``vocab``: only tokens below it.  ``positional`` says whether anything depends on i (default: masks given, or an automaton with
+    a rejecting state); where nothing does, Nt = 1 and M[0] is the greatest fixed point of the recursion -- only transitions into states
+    without an infinite continuation are pruned, and one row serves a generation of any length.  Otherwise Nt = N, N S <= 2^22."""
+    A, N = automaton, int(N)
+    S, V = A.S, A.V
+    Vlive = V if vocab is None else int(vocab)
+    e = None if eos is None or not 0 <= int(eos) < V else int(eos)
+    ok = A.delta >= 0                                            # (S, V)
+    to = A.delta.clamp(min=0).to(torch.int64)
+    ok[:, Vlive:] = False
+    if e is not None:
+        ok[:, e] = False
+    cols = torch.arange(V)
+    if masks is None:
+        P = torch.ones(max(N, 1), V, dtype=torch.bool)
+    else:
+        P = ((masks.detach().cpu().to(torch.int64)[:, None] >> cols[None]) & 1).bool()      # (N, V)
+    if positional is None:
+        positional = masks is not None or not bool(A.accept.all())
+    ends = torch.zeros(S, V, dtype=torch.bool)                   # eos, where the state accepts
+    if e is not None and e < Vlive:
+        ends[:, e] = A.accept
+    if not positional:
+        live = torch.ones(S, dtype=torch.bool)
+        while True:
+            bits = ((ok & live[to]) | ends) & P[0][None]
+            new = bits.any(1)
+            if bool((new == live).all()):
+                return _mask_ints(bits)[None].contiguous()
+            live = new
+    if N * S > _lib.AUTOMATON_MAX_TABLE:
+        raise ValueError(f"an automaton of {S} states over {N} new tokens needs a step table of {N * S} entries: the limit is "
+                         f"{_lib.AUTOMATON_MAX_TABLE} (2^22)")
+    M = torch.zeros(max(N, 1), S, dtype=torch.int64)
+    live = A.accept.clone()
+    for i in range(N - 1, -1, -1):
+        bits = ((ok & live[to]) | ends) & P[i][None]
+        M[i] = _mask_ints(bits)
+        live = bits.any(1)
+    return M

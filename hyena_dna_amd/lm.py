@@ -404,6 +404,46 @@ def _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G,
     return allow, check
 
 
+def _automaton_tables(automaton, input_ids, lengths, fan, N, V, vocab_size, allowed_tokens, constraints, min_new_tokens, eos_token_id):
+    """generate()'s ``automaton`` as the tables of the device sampler / beam searcher -> (M (Nt, S) int64, delta (S, V) int32, dstate
+    (G fan,) int32) on the input's device.  Everything that can be refused is refused here, before a cache exists: per-row positional masks,
+    an automaton over another alphabet than the logits', a table over the limit, a row whose prompt leaves no accepted continuation.  One
+    read-back: the last ``context`` prompt tokens of every row (and the positional masks, where there are any)."""
+    from .inference import TokenAutomaton, automaton_step_tables
+    A, dev = automaton, input_ids.device
+    if not isinstance(A, TokenAutomaton):
+        raise ValueError(f"automaton must be an inference.TokenAutomaton (got {type(A).__name__})")
+    G, P = input_ids.shape
+    if torch.is_tensor(constraints) and constraints.dim() != 1:
+        raise ValueError(f"generate(automaton=...) takes positional constraints of shape ({N},), one row for the batch: per-row masks "
+                         f"{tuple(constraints.shape)} together with an automaton are out of scope")
+    if A.V != V:
+        raise ValueError(f"the automaton reads {A.V} tokens (the columns of delta) and the logits have {V} columns")
+    Vlive = V if vocab_size is None else int(vocab_size)
+    allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G, fan, N, dev)
+    check_masks(V, Vlive)
+    # nothing depends on the position where the masks are one set for every token (allowed_tokens alone) and eos is not held back
+    positional = constraints is not None or bool(int(min_new_tokens)) or not bool(A.accept.all())
+    M = automaton_step_tables(A, N, masks=allow, eos=eos_token_id, vocab=Vlive, positional=positional)
+    ctx = min(A.context, P)
+    if ctx == 0:
+        tails = [[] for _ in range(G)]
+    elif lengths is None:
+        tails = input_ids[:, P - ctx:].tolist()
+    else:                                              # the tokens in front of lengths[b]
+        idx = lengths.to(torch.int64)[:, None] - ctx + torch.arange(ctx, device=dev)
+        got = torch.stack([input_ids.gather(1, idx.clamp(min=0)), idx]).tolist()
+        tails = [[v for v, j in zip(row, at) if j >= 0] for row, at in zip(*got)]
+    s0 = [A.initial_state(t) for t in tails]
+    live0 = M[0] != 0
+    for g, st in enumerate(s0):
+        if not bool(live0[st]):
+            raise ValueError(f"row {g}: after its prompt the automaton stands in state {st}, from which no accepted word of {N} new tokens "
+                             "exists under these constraints")
+    dstate = torch.tensor(s0, dtype=torch.int32).repeat_interleave(fan).to(dev)
+    return M.to(dev), A.delta.to(dev), dstate
+
+
 class GenerationMixin:
     """Greedy / top-k sampling.  Default: by re-running the causal model on the growing prefix (the reference's way: its HyenaOperator
     ignores ``inference_params``).  ``use_cache=True``: one prefill that fills every layer's decode cache, then one incremental step per
@@ -417,7 +457,7 @@ class GenerationMixin:
     def generate(self, input_ids, max_length, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False, use_cache=False,
                  cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None, sampler=None,
                  stop_check_every=0, num_return_sequences=1, lookahead=None, allowed_tokens=None, constraints=None, min_new_tokens=0,
-                 output_logprobs=False, num_beams=None, **kwargs):
+                 output_logprobs=False, num_beams=None, automaton=None, **kwargs):
         """``lengths`` (device int32 (B,), 1 <= lengths[b] <= P): ``input_ids`` (B, P) is right-padded and row b's prompt is its first
         lengths[b] tokens.  Every row then gets N = max_length - P new tokens, row b's i-th at column lengths[b] + i of the returned
         (B, max_length) ``sequences``; the columns from lengths[b] + N on hold ``pad_token_id`` (default: the model's ``pad_token_id``
@@ -473,14 +513,27 @@ class GenerationMixin:
         as it is), ``pad_token_id``, ``vocab_size``, ``stop_check_every``, ``cg``.  A beam that no allowed token can continue with a
         finite probability has score -inf.  Refused: ``use_cache=False``, ``sampler="torch"``, ``top_k > 1``, ``top_p != 1``,
         ``temperature != 1``, ``seed``, ``output_scores``, ``lengths``, ``lookahead``, n > k, logits of more than 64 columns.  Out of
-        scope: a length penalty or any length normalisation, diverse or sampled beams, beams on ragged or lookahead caches."""
+        scope: a length penalty or any length normalisation, diverse or sampled beams, beams on ragged or lookahead caches.
+
+        ``automaton=A`` (``inference.TokenAutomaton``, ``inference.motif_automaton``; device sampler and beams only, selects the device
+        sampler when ``sampler`` is None): every returned row, up to its eos or to N new tokens, spells a word the automaton accepts --
+        no restriction site on either strand, no homopolymer longer than h, a required motif somewhere, any regular language of at most
+        4096 states over the logit columns.  The allowed set of a row depends on what the row has emitted: its state lives in device
+        memory next to ``col`` and the sampler (the beam kernel) looks the mask up in a table computed backwards from the end on entry, so
+        a row can never paint itself into a corner and a constrained generation is still N - 1 replays with ``cg=True``.  The last
+        ``A.context`` prompt tokens set the initial state.  Composes with everything above: ``allowed_tokens``, ``constraints`` ((N,)
+        only), ``min_new_tokens``, ``eos_token_id`` (allowed only in an accepting state), ``vocab_size``, ``top_k``, ``top_p``,
+        ``temperature``, ``seed``, ``lengths``, ``num_return_sequences``, ``lookahead``, ``stop_check_every``, ``output_scores``,
+        ``output_logprobs``, ``num_beams``, ``cg``.  ValueError: ``sampler="torch"``, ``use_cache=False``, (B, N) constraints, an
+        automaton whose ``delta`` has another number of columns than the logits, a prompt after which no accepted word of N tokens
+        exists (the row is named), N S over 2^22 where the table depends on the position."""
         if num_beams is not None and int(num_beams) != 1:
             return self._generate_beam(input_ids, max_length, int(num_beams), int(num_return_sequences), top_k=top_k, temperature=temperature,
                                        return_dict_in_generate=return_dict_in_generate, output_scores=output_scores, use_cache=use_cache,
                                        cg=cg, lengths=lengths, pad_token_id=pad_token_id, top_p=top_p, eos_token_id=eos_token_id, seed=seed,
                                        vocab_size=vocab_size, sampler=sampler, stop_check_every=int(stop_check_every), lookahead=lookahead,
                                        allowed_tokens=allowed_tokens, constraints=constraints, min_new_tokens=min_new_tokens,
-                                       output_logprobs=output_logprobs)
+                                       output_logprobs=output_logprobs, automaton=automaton)
         if cg and not use_cache:
             raise ValueError("generate(cg=True) replays the cached step: it needs use_cache=True")
         from .inference import check_lookahead
@@ -502,7 +555,8 @@ class GenerationMixin:
         wants_device = [n for n, on in (("top_p", top_p is not None and float(top_p) != 1.0), ("eos_token_id", eos_token_id is not None),
                                         ("seed", seed is not None), ("vocab_size", vocab_size is not None),
                                         ("allowed_tokens", allowed_tokens is not None), ("constraints", constraints is not None),
-                                        ("min_new_tokens", bool(min_new_tokens)), ("output_logprobs", bool(output_logprobs))) if on]
+                                        ("min_new_tokens", bool(min_new_tokens)), ("output_logprobs", bool(output_logprobs)),
+                                        ("automaton", automaton is not None)) if on]
         if sampler is None:
             sampler = "device" if wants_device else "torch"
         if sampler not in ("torch", "device"):
@@ -511,7 +565,7 @@ class GenerationMixin:
             return self._generate_device(input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
                                          use_cache, cg, 1.0 if top_p is None else float(top_p), eos_token_id, seed, vocab_size,
                                          int(stop_check_every), fan=n, lookahead=W, allowed_tokens=allowed_tokens, constraints=constraints,
-                                         min_new_tokens=min_new_tokens, output_logprobs=output_logprobs)
+                                         min_new_tokens=min_new_tokens, output_logprobs=output_logprobs, automaton=automaton)
         if wants_device or stop_check_every:
             raise ValueError(f"sampler='torch' does not serve {', '.join(wants_device + ['stop_check_every'] * bool(stop_check_every))}: "
                              "use sampler='device'")
@@ -558,7 +612,7 @@ class GenerationMixin:
 
     def _generate_device(self, input_ids, max_length, lengths, pad_token_id, top_k, temperature, return_dict_in_generate, output_scores,
                          use_cache, cg, top_p, eos_token_id, seed, vocab_size, stop_check_every, fan=1, lookahead=0, allowed_tokens=None,
-                         constraints=None, min_new_tokens=0, output_logprobs=False):
+                         constraints=None, min_new_tokens=0, output_logprobs=False, automaton=None):
         """generate() with the device sampler: the prefill, one eager sampler call on its last logits (row b's own last position for ragged
         prompts), then N - 1 steps that each end with the sampler kernel writing the next step's input ids in place -- with ``cg`` N - 1
         graph replays and no tensor work between them.  ``sequences`` is one (B, max_length) tensor allocated up front.  ``fan = n > 1``:
@@ -600,13 +654,24 @@ class GenerationMixin:
             seq[:, :P] = input_ids if fan == 1 else input_ids.repeat_interleave(fan, 0)
             col = torch.full((B,), P, dtype=torch.int32, device=dev)
         smp, n_done = None, 0
+        tables = None
+        if automaton is not None and N > 0:            # every refusal before a cache exists; V from the head (checked against the logits below)
+            head = getattr(self, "lm_head", None)
+            V_head = head.weight.shape[0] if torch.is_tensor(getattr(head, "weight", None)) else automaton.V
+            if vocab_size is not None and not 1 <= int(vocab_size) <= V_head:
+                raise ValueError(f"vocab_size={vocab_size}: the logits have {V_head} columns")
+            tables = _automaton_tables(automaton, input_ids, lengths, fan, N, V_head, vocab_size, allowed_tokens, constraints, min_new_tokens,
+                                       eos_token_id)
         if N > 0:
             ip = InferenceParams(max_seqlen=P + N, max_batch_size=B, lengths_per_sample=lengths, lookahead=lookahead)
             ip.key_value_memory_dict = self.allocate_inference_cache(B, P + N, **({} if fan == 1 else dict(fan=fan, prompt_len=P)),
                                                                      **(dict(lookahead=lookahead) if lookahead else {}))
             if ip.key_value_memory_dict is None:
                 raise NotImplementedError(f"{type(self).__name__} has no decode cache: generate(use_cache=True) is not available")
-            allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, B // fan, fan, N, dev)
+            if tables is None:
+                allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, B // fan, fan, N, dev)
+            else:                                      # (the positional masks are inside M)
+                allow, check_masks = None, lambda V, Vlive: None
             out = self(input_ids, inference_params=ip)
             logits = out[0] if isinstance(out, tuple) else out
             logits = logits.logits if hasattr(logits, "logits") else logits                        # (B, P, V); fan > 1: (B / fan, P, V)
@@ -623,8 +688,11 @@ class GenerationMixin:
                 seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if top_k > 1 else 0
             seed = torch.tensor([int(seed)], dtype=torch.int64).to(dev)
             check_masks(V, V if vocab_size is None else int(vocab_size))
+            if tables is not None and tables[1].shape[1] != V:
+                raise ValueError(f"the automaton reads {tables[1].shape[1]} tokens (the columns of delta) and the logits have {V} columns")
             smp = DeviceSampler(seq, col, seed, temperature=temperature, top_k=top_k, top_p=top_p, eos=eos_token_id, pad=pad_token_id,
-                                vocab=vocab_size, want_scores=output_scores, V=V, allow=allow, want_logprobs=output_logprobs, n_new=N)
+                                vocab=vocab_size, want_scores=output_scores, V=V, allow=allow, want_logprobs=output_logprobs, n_new=N,
+                                **({} if tables is None else dict(automaton_tables=tables)))
             ip.seqlen_offset = P                       # ragged: the furthest any row has got (bounds checks only)
             step = GraphedDecodeStep(self, ip, B, sampler=smp) if cg and N > 1 else None
             nxt = step.ids if step is not None else torch.empty(B, 1, dtype=torch.int64, device=dev)
@@ -666,7 +734,7 @@ class GenerationMixin:
     def _generate_beam(self, input_ids, max_length, k, n, top_k=1, temperature=1.0, return_dict_in_generate=False, output_scores=False,
                        use_cache=False, cg=False, lengths=None, pad_token_id=None, top_p=1.0, eos_token_id=None, seed=None, vocab_size=None,
                        sampler=None, stop_check_every=0, lookahead=None, allowed_tokens=None, constraints=None, min_new_tokens=0,
-                       output_logprobs=False):
+                       output_logprobs=False, automaton=None):
         """generate(num_beams=k): the prefill over the G prompts into a fan-out cache (fan = k), one eager beam step on its last logits,
         then N - 1 steps that each end with the beam kernel and the caches' re-parenting (``inference.BeamSearcher``) -- with ``cg`` N - 1
         graph replays -- and one backtrack over the records.  Every refusal comes before a cache is built."""
@@ -714,7 +782,13 @@ class GenerationMixin:
                 return seq
             values = [seq, None, torch.zeros(G * n, dtype=torch.float32, device=dev)] + [torch.empty(G * n, 0, device=dev)] * bool(output_logprobs)
             return namedtuple("BeamSearchDecoderOnlyOutput", fields)(*values)
-        allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G, k, N, dev)
+        tables = None
+        if automaton is not None:                      # every refusal before a cache exists; the positional masks go into M
+            tables = _automaton_tables(automaton, input_ids, None, k, N, automaton.V if V is None else V, vocab_size, allowed_tokens,
+                                       constraints, min_new_tokens, eos_token_id)
+            allow, check_masks = None, lambda V, Vlive: None
+        else:
+            allow, check_masks = _allowed_masks(allowed_tokens, constraints, min_new_tokens, eos_token_id, G, k, N, dev)
         if V is not None:
             check_masks(V, V if vocab_size is None else int(vocab_size))
         ip = InferenceParams(max_seqlen=P + N, max_batch_size=B)
@@ -731,8 +805,11 @@ class GenerationMixin:
             if vocab_size is not None and not 1 <= int(vocab_size) <= V:
                 raise ValueError(f"vocab_size={vocab_size}: the logits have {V} columns")
             check_masks(V, V if vocab_size is None else int(vocab_size))
+        if tables is not None and tables[1].shape[1] != logits.shape[-1]:
+            raise ValueError(f"the automaton reads {tables[1].shape[1]} tokens (the columns of delta) and the logits have {logits.shape[-1]} columns")
         last = logits[:, -1].repeat_interleave(k, 0)
-        search = BeamSearcher(ip.key_value_memory_dict.values(), input_ids, k, N, eos=eos_token_id, pad=pad_token_id, vocab=vocab_size, allow=allow)
+        search = BeamSearcher(ip.key_value_memory_dict.values(), input_ids, k, N, eos=eos_token_id, pad=pad_token_id, vocab=vocab_size, allow=allow,
+                              **({} if tables is None else dict(automaton_tables=tables)))
         ip.seqlen_offset = P
         step = GraphedDecodeStep(self, ip, B, sampler=search) if cg and N > 1 else None
         nxt = step.ids if step is not None else torch.empty(B, 1, dtype=torch.int64, device=dev)

@@ -233,6 +233,41 @@ int hyena_decode_reorder_fan(void* vgr, float* tail, const int* parent, const in
 int hyena_decode_beam_backtrack(const int* tok_hist, const int* parent_hist, const float* lp_hist, long ldh, int B, int fan, int n_done,
                                 int n_ret, long long* seq, long lds, int P, float* logprobs, long ldp, void* stream);
 
+/* Automaton-constrained generation: the allowed set of a row depends on the tokens the row itself has emitted, through the state of a
+ * deterministic automaton over the token alphabet that the row carries in device memory.
+ *   delta  (S, V) int32, V the number of logit columns: delta[s V + v] is the state after token v in state s, -1 where v is forbidden there;
+ *   M      (Nt, S) 64-bit masks: bit v of M[n S + s] says that token v may be the row's n-th new token in state s -- the host computes it
+ *          backwards from the end (an accepting state after the last token, positional masks, eos and min_new_tokens folded in), so a row
+ *          that follows M can always be completed to a word of the language.  Nt == 1: nothing depends on n, row 0 serves every token;
+ *   dstate (B,) int32: the state of every row, initialised by the caller (the automaton run over the end of the prompt).
+ * 1 <= S <= HYENA_DECODE_AUTOMATON_MAX_STATES, Nt >= 1, Nt S <= HYENA_DECODE_AUTOMATON_MAX_TABLE.
+ *
+ * hyena_decode_sample_automaton -- hyena_decode_sample_constrained with the row's mask M[(Nt == 1 ? 0 : n) S + s], s = dstate[b],
+ * n = col[b] - start[b].  Everything after the mask is that function operation for operation: A (a mask with no bit below Vlive: the
+ * whole live vocabulary), ranks among A, greedy, top-k, top-p, the Philox word of (seed, row, column), eos, pad, scores, u_out and the
+ * log-prob over all live tokens.  After the token is chosen dstate[b] = delta[s V + tok].  The state is left as it is for a finished row,
+ * for a row that has just emitted eos, for a -1 transition (reachable only through the whole-vocabulary fall-back) and for an s outside
+ * [0, S); such a row, and with Nt > 1 a row whose n lies outside [0, Nt), samples unmasked.  Parked rows touch nothing.  With S = 1,
+ * delta == 0 and M one row of masks the results equal hyena_decode_sample_constrained's with allow = M, lda = 0, bit for bit.
+ * Bad arguments as for hyena_decode_sample_constrained, and: a null M, delta, dstate or start, S or Nt S out of range, Vdelta (the number of
+ * columns of delta) != V -- HYENA_ERR_BAD_ARG before anything is launched.
+ *
+ * hyena_decode_beam_automaton -- hyena_decode_beam with row j's allowed set M[(Nt == 1 ? 0 : n) S + dstate[row j]] (the same fall-backs).
+ * All k states of a group are read before any of its rows is written.  Rank r, which continues row p with token tok, receives
+ * dstate = delta[dstate_old[p] V + tok]; the parent's state as it is for a finished beam's pad candidate, for eos, for a -1 transition and
+ * for a state outside [0, S).  The order, the selection and the records are hyena_decode_beam's; hyena_decode_reorder_fan is not involved
+ * (the state travels inside this kernel).  Bad arguments as for hyena_decode_beam and as above. */
+#define HYENA_DECODE_AUTOMATON_MAX_STATES 4096
+#define HYENA_DECODE_AUTOMATON_MAX_TABLE (1L << 22)
+int hyena_decode_sample_automaton(const void* logits, long ldl, int dtype, int B, int V, int Vlive, float temperature, int top_k, float top_p,
+                                  const unsigned long long* seed, int eos, int pad, int* col, int* done, long long* seq, long lds, int ncols,
+                                  long long* next, long ldn, float* scores, float* u_out, const unsigned long long* M, int Nt, int S,
+                                  const int* delta, int Vdelta, int* dstate, const int* start, float* logprobs, long ldp, void* stream);
+int hyena_decode_beam_automaton(const void* logits, long ldl, int dtype, int B, int fan, int V, int Vlive, int eos, int pad, int* col,
+                                int* done, float* beam_score, const int* start, int* parent, long long* next, long ldn, int ncols,
+                                const unsigned long long* M, int Nt, int S, const int* delta, int Vdelta, int* dstate, int* tok_hist,
+                                int* parent_hist, float* lp_hist, long ldh, int nrec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
