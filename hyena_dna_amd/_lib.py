@@ -209,6 +209,12 @@ def lib():
         L.hyena_decode_post_la.restype = c_int
         L.hyena_decode_post_la.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                            c_int, c_int, c_int, c_void_p]
+        # edited windows of a reference sequence (include/hyena_variant.h)
+        L.hyena_variant_pre.restype = c_int
+        L.hyena_variant_pre.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int, c_int, c_int, c_int, c_void_p]
+        L.hyena_variant_conv.restype = c_int
+        L.hyena_variant_conv.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
         L.hyena_decode_sample.restype = c_int
         L.hyena_decode_sample.argtypes = [c_void_p, ctypes.c_long, c_int, c_int, c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_int, c_void_p, ctypes.c_long,
@@ -1158,6 +1164,46 @@ def decode_post_la(part, carry, hist, fb, x0, z, pos, base, B, Lcap):
         check(lib().hyena_decode_post_la(part.data_ptr(), carry.data_ptr(), hist.data_ptr(), None if fb is None else fb.data_ptr(),
                                          x0.data_ptr(), z.data_ptr(), pos.data_ptr(), base.data_ptr(), int(B), D, int(Lcap), lda, W,
                                          dtype_code(hist.dtype), _backend.stream(z.device)))
+
+
+# ---- edited windows of a reference sequence (include/hyena_variant.h): M windows of T positions, window m starting at pos[m].  x3 (M, T, 3D) the
+# in_proj output without bias, tail (3D, M, 2) fp32, pos (M,) int32, vg_ref (M, D, T) in x3's type, x0 (M, T, D) and delta / y_ref (M, D, T) fp32,
+# z (M, T, D) in the I/O type; all contiguous ----
+VARIANT_TMAX = 1024          # HYENA_VARIANT_TMAX: positions per window
+
+
+def variant_pre(x3, bin_, w, b, tail, pos, vg_ref, x0, delta):
+    """x0 = the gate, delta = float(round_io(v * x1)) - float(vg_ref) of every window position; -> VARIANT_TMAX"""
+    _require_gpu(x3, "x")
+    M, T, D3 = x3.shape
+    D = D3 // 3
+    assert x3.is_contiguous() and D3 == 3 * D and vg_ref.dtype == x3.dtype and vg_ref.shape == (M, D, T) and vg_ref.is_contiguous()
+    assert tail.dtype == torch.float32 and tail.shape == (D3, M, 2) and tail.is_contiguous()
+    assert pos.dtype == torch.int32 and pos.shape == (M,) and pos.is_contiguous()
+    assert x0.dtype == torch.float32 and x0.shape == (M, T, D) and x0.is_contiguous()
+    assert delta.dtype == torch.float32 and delta.shape == (M, D, T) and delta.is_contiguous()
+    with _backend.guard(x3.device):
+        check(lib().hyena_variant_pre(x3.data_ptr(), D3, None if bin_ is None else bin_.data_ptr(), w.data_ptr(), b.data_ptr(), tail.data_ptr(),
+                                      pos.data_ptr(), vg_ref.data_ptr(), x0.data_ptr(), delta.data_ptr(), M, D, T, dtype_code(x3.dtype),
+                                      _backend.stream(x3.device)))
+    return VARIANT_TMAX
+
+
+def variant_conv(y_ref, delta, k, fb, x0, z):
+    """z (M, T, D) = round(round(y_ref + the causal product of k[:, :T] with delta + fb delta) * x0); k (D, >= T) fp32 rows contiguous; -> VARIANT_TMAX"""
+    _require_gpu(z, "z")
+    M, T, D = z.shape
+    assert z.is_contiguous() and z.dtype in _DTYPES
+    assert k.dtype == torch.float32 and k.dim() == 2 and k.stride(1) == 1 and k.shape[0] == D and k.shape[1] >= T
+    for t in (y_ref, delta):
+        assert t.dtype == torch.float32 and t.shape == (M, D, T) and t.is_contiguous()
+    assert x0.dtype == torch.float32 and x0.shape == (M, T, D) and x0.is_contiguous()
+    with _backend.guard(z.device):
+        check(lib().hyena_variant_conv(y_ref.data_ptr(), delta.data_ptr(), k.data_ptr(), k.stride(0) if D > 1 else max(k.shape[1], T),
+                                       None if fb is None else fb.data_ptr(), x0.data_ptr(), z.data_ptr(), M, D, T, dtype_code(z.dtype),
+                                       _backend.stream(z.device)))
+    return VARIANT_TMAX
+
 
 
 # ---- token sampling, the last node of the per-token step (hyena_decode_sample): one wavefront per logit row ------------------------------------

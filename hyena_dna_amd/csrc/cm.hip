@@ -1,11 +1,13 @@
 // cm.hip -- host side of the channel-major operator shell (cm_kernels.h; C ABI in include/hyena_mixer.h) and of its one-position decode
-// step (decode_kernels.h; C ABI in include/hyena_decode.h).
+// step (decode_kernels.h; C ABI in include/hyena_decode.h) and of the edited-window step (variant_kernels.h; C ABI in include/hyena_variant.h).
 #include "cm_kernels.h"
 #include "decode_kernels.h"
+#include "variant_kernels.h"
 #include "launch.h"
 #include "../../include/hyena_fftconv.h"
 #include "../../include/hyena_mixer.h"
 #include "../../include/hyena_decode.h"
+#include "../../include/hyena_variant.h"
 
 using namespace hyena;
 
@@ -544,6 +546,42 @@ int hyena_decode_beam_backtrack(const int* tok_hist, const int* parent_hist, con
     a.B = B; a.fan = fan; a.n_done = n_done; a.n_ret = n_ret; a.P = P;
     const int rows = B / fan * n_ret;
     HY_LAUNCH(decode_beam_backtrack_kernel, dim3((rows + DEC_THREADS - 1) / DEC_THREADS), dim3(DEC_THREADS), 0, stream, a);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+}  // extern "C"
+
+// ---- edited windows of a reference sequence (variant_kernels.h) ---------------------------------------------------------------------------
+static_assert(VAR_TMAX == HYENA_VARIANT_TMAX, "the header's window limit");
+namespace {
+bool var_shape_ok(int M, int D, int T, int dtype) {
+    return M >= 1 && D >= 1 && D <= 65535 && T >= 1 && T <= VAR_TMAX && (long)M * T * D <= (1L << 38) && dec_dtype_ok(dtype);
+}
+}  // namespace
+
+extern "C" {
+
+int hyena_variant_pre(const void* x3, int ldx, const float* bin, const float* w, const float* b, const float* tail, const int* pos,
+                      const void* vg_ref, float* x0, float* delta, int M, int D, int T, int dtype, void* stream) {
+    if (x3 == nullptr || w == nullptr || b == nullptr || tail == nullptr || pos == nullptr || vg_ref == nullptr || x0 == nullptr ||
+        delta == nullptr || !var_shape_ok(M, D, T, dtype) || ldx < 3 * D)
+        return HYENA_ERR_BAD_ARG;
+    VarPreArgs a;
+    a.x = x3; a.bin = bin; a.w = w; a.b = b; a.tail = tail; a.pos = pos; a.vg_ref = vg_ref; a.x0 = x0; a.delta = delta;
+    a.M = M; a.D = D; a.T = T; a.ldx = ldx;
+    HY_DEC_DISPATCH(variant_pre_kernel, dim3((unsigned)(((size_t)M * T * D + VAR_THREADS - 1) / VAR_THREADS)), VAR_THREADS, 0);
+    return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
+}
+
+int hyena_variant_conv(const float* y_ref, const float* delta, const float* k, int ldk, const float* fb, const float* x0, void* z, int M, int D,
+                       int T, int dtype, void* stream) {
+    if (y_ref == nullptr || delta == nullptr || k == nullptr || x0 == nullptr || z == nullptr || !var_shape_ok(M, D, T, dtype) || ldk < T)
+        return HYENA_ERR_BAD_ARG;
+    VarConvArgs a;
+    a.y_ref = y_ref; a.delta = delta; a.k = k; a.fb = fb; a.x0 = x0; a.z = z;
+    a.M = M; a.D = D; a.T = T; a.ldk = ldk;
+    a.cw = var_cw(D, T); a.pp = var_pairs(T); a.stride = var_stride(T);
+    HY_DEC_DISPATCH(variant_conv_kernel, dim3(M, (D + a.cw - 1) / a.cw), VAR_THREADS, (size_t)2 * a.cw * a.stride * sizeof(float));
     return hy_launch_error() ? HYENA_ERR_LAUNCH : HYENA_OK;
 }
 

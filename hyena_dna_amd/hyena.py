@@ -434,9 +434,10 @@ class HyenaOperator(nn.Module):
         fside.join(ks)
         return ks, fb, x, vg
 
-    def _forward_fused_cm(self, u, l_filter, keep_vg=False):
+    def _forward_fused_cm(self, u, l_filter, keep_vg=False, keep_filter=False):
         """the fused channel-major route -> (y, xT, vg).  keep_vg: vg is made here (cm_pre_fwd on xT, what the mixer would run itself) when
-        the projection kernel does not hand it back -- the same kernel on the same operands, so y does not change by a bit."""
+        the projection kernel does not hand it back -- the same kernel on the same operands, so y does not change by a bit.
+        keep_filter: -> (y, xT, vg, k, fb), the filter and the convolution bias the route evaluated anyway."""
         (k,), fb, xT, vg = self._filters_and_in_proj(u, l_filter)
         if keep_vg and vg is None:
             from . import _lib
@@ -449,6 +450,8 @@ class HyenaOperator(nn.Module):
             zT = hyena_mixer_core_cm(xT, self.in_proj.bias, self.short_filter.weight, self.short_filter.bias, k, fb, l_filter,
                                      vg=vg)
             y = out_proj_cm(zT, self.out_proj.weight, self.out_proj.bias)   # activation is the identity (_fused_ok)
+        if keep_filter:
+            return y, xT, vg, k, fb
         return y, xT, vg
 
     # ---- incremental decoding (hyena_dna_amd/inference.py, csrc/decode_kernels.h) ----------------------------------------------------------------
@@ -529,8 +532,39 @@ class HyenaOperator(nn.Module):
             y = hyena_linear(z.view(B, 1, self.d_model), self.out_proj.weight, self.out_proj.bias)
         return (y, None) if self.return_state else y
 
+    # ---- edited windows of a reference sequence (hyena_dna_amd/variants.py, csrc/variant_kernels.h) ------------------------------------------
+    def _forward_edit_windows(self, u, ew):
+        """forward(u, inference_params=ew) with ``ew`` an ``EditWindowParams``.  Reference phase, u (G, L, D): the prefill's route -- the plain
+        forward, bit for bit -- which also keeps, for the M windows only, what the window phase needs (``EditWindowParams.store_reference``).
+        Window phase, u (M, T, D): in_proj -> variant_pre -> variant_conv -> out_proj, the operator's output at positions
+        ``positions[m] ... positions[m] + T - 1`` of the sequence that equals the reference below ``positions[m]`` and whose layer input from
+        there on is ``u[m]``.  No history is read."""
+        from .inference import check_decodable
+        check_decodable(self)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError("edited windows are inference only: run them under torch.no_grad() / torch.inference_mode(), or freeze the parameters")
+        if u.dim() != 3 or u.shape[-1] != self.d_model:
+            raise ValueError(f"edited windows take (batch, positions, {self.d_model}) inputs (got {tuple(u.shape)})")
+        key = self._decode_key()
+        if ew.phase == "reference":
+            l = u.shape[1]
+            check_decodable(self, max_seqlen=l)
+            y, xT, vg, k, fb = self._forward_fused_cm(u, l, keep_vg=True, keep_filter=True)
+            ew.store_reference(key, self, xT, vg, k, fb, l)
+        else:
+            st = ew.layers.get(key)
+            if st is None:
+                raise ValueError("the window phase of EditWindowParams comes after its reference phase: this operator has kept no reference "
+                                 "windows (run the reference sequence with phase = 'reference' first)")
+            x = hyena_linear(u, self.in_proj.weight, None)                       # (M, T, 3D): the forward's 16-bit weight shadows / autocast
+            y = hyena_linear(ew.step(st, x), self.out_proj.weight, self.out_proj.bias)
+        return (y, None) if self.return_state else y
+
     def forward(self, u, *args, inference_params=None, **kwargs):
         if inference_params is not None:
+            from .variants import EditWindowParams
+            if isinstance(inference_params, EditWindowParams):
+                return self._forward_edit_windows(u, inference_params)
             return self._forward_cached(u, inference_params)
         l = u.size(-2)
         l_filter = min(l, self.l_max)

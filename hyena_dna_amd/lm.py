@@ -1236,6 +1236,139 @@ class HyenaDNALM(nn.Module, GenerationMixin):
         logprobs = torch.log_softmax(logits[..., :V], dim=-1).gather(-1, continuations.long().unsqueeze(-1)).squeeze(-1)
         return (logprobs, logits) if return_logits else logprobs
 
+    # ---- variant effect scoring: one reference pass, edited windows on device (hyena_dna_amd/variants.py) ---------------------------------
+    def _check_edit_windows(self, ref_ids, positions, groups, T, what="T"):
+        """the refusals every edited-window entry point shares, before any work -> (G, L, M, groups)"""
+        from . import _lib
+        from .inference import check_decodable
+        if self.backbone.embeddings.max_position_embeddings > 0:
+            raise NotImplementedError("edited windows need a model without learned position embeddings (max_position_embeddings = 0): a "
+                                      "window row would need its absolute position's embedding")
+        if not torch.is_tensor(ref_ids) or ref_ids.dim() != 2 or ref_ids.dtype != torch.int64 or ref_ids.shape[0] < 1 or ref_ids.shape[1] < 1:
+            raise ValueError("ref_ids has to be a (G >= 1, L >= 1) int64 tensor of token ids")
+        G, L = ref_ids.shape
+        if not 1 <= int(T) <= _lib.VARIANT_TMAX:
+            raise ValueError(f"{what}={T}: a window holds 1 ... {_lib.VARIANT_TMAX} positions")
+        if not torch.is_tensor(positions) or positions.dim() != 1 or positions.dtype != torch.int64 or positions.shape[0] < 1:
+            raise ValueError("positions has to be an (M >= 1,) int64 tensor")
+        if positions.device != ref_ids.device:
+            raise ValueError(f"positions live on {positions.device}, ref_ids on {ref_ids.device}")
+        M = positions.shape[0]
+        if groups is None:
+            if G != 1:
+                raise ValueError(f"groups is required with {G} reference rows: the row of every variant")
+            groups = torch.zeros_like(positions)
+        if not torch.is_tensor(groups) or groups.shape != (M,) or groups.dtype != torch.int64 or groups.device != ref_ids.device:
+            raise ValueError(f"groups has to be an ({M},) int64 tensor on {ref_ids.device}")
+        for m in self._mixers():
+            if not hasattr(m, "_forward_edit_windows"):
+                raise NotImplementedError(f"edited windows are served by HyenaOperator mixers only (got {type(m).__name__})")
+            check_decodable(m, max_seqlen=L)
+        if int(positions.min()) < 0 or int(positions.max()) >= L:
+            raise ValueError(f"positions hold entries outside [0, {L})")
+        if int(groups.min()) < 0 or int(groups.max()) >= G:
+            raise ValueError(f"groups hold entries outside [0, {G})")
+        return G, L, M, groups
+
+    @torch.no_grad()
+    def forward_edited_windows(self, ref_ids, positions, window_tokens, groups=None, max_window_tokens=None):
+        """``ref_ids`` (G, L), ``positions`` (M,), ``window_tokens`` (M, T) -> ``(ref_logits (G, L, V), logits (M, T, V))``:
+        ``logits[m, i]`` is the model's logits at position ``positions[m] + i`` of the sequence that equals ``ref_ids[groups[m]]`` with
+        positions ``[positions[m], positions[m] + T)`` replaced by ``window_tokens[m]``; rows with ``positions[m] + i >= L`` are zeros.
+
+        ONE forward over the reference (the cached prefill's route: ``ref_logits`` are its logits bit for bit) serves all M edits; every
+        edit then costs T positions through the per-position layers and a T x T triangular product per channel and layer -- exact, because
+        the long convolution is linear in its input (hyena_dna_amd/variants.py).  Nothing of the result beyond ``positions[m] + T - 1`` is
+        computed.  ``groups`` (M,): the reference row of every edit (None with G = 1).  ``max_window_tokens``: the window pass runs
+        ``max(1, max_window_tokens // T)`` windows at a time, which bounds its activations; the kept reference windows are 6 M T d_model
+        bytes per layer (2-byte I/O) whatever it is.  All ids int64 on the model's device; 1 <= T <= 1024."""
+        from .variants import EditWindowParams
+        if not torch.is_tensor(window_tokens) or window_tokens.dim() != 2 or window_tokens.dtype != torch.int64:
+            raise ValueError("window_tokens has to be an (M, T) int64 tensor of token ids")
+        T = window_tokens.shape[1]
+        G, L, M, groups = self._check_edit_windows(ref_ids, positions, groups, T, what="window_tokens' T")
+        if window_tokens.shape[0] != M or window_tokens.device != ref_ids.device:
+            raise ValueError(f"window_tokens has to be ({M}, T) on {ref_ids.device} (got {tuple(window_tokens.shape)} on {window_tokens.device})")
+        per = M if max_window_tokens is None else max(1, int(max_window_tokens) // T)
+        if max_window_tokens is not None and int(max_window_tokens) < 1:
+            raise ValueError(f"max_window_tokens={max_window_tokens}: at least one token")
+        ew = EditWindowParams(positions, groups, T)
+        ref_logits = self(ref_ids, inference_params=ew)[0].logits
+        ew.phase = "window"
+        outs = []
+        for lo in range(0, M, per):
+            hi = min(lo + per, M)
+            ew.select(lo, hi)
+            outs.append(self(window_tokens[lo:hi], inference_params=ew)[0].logits)
+        logits = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        past = (positions[:, None] + torch.arange(T, device=positions.device)[None, :]) >= L
+        return ref_logits, logits.masked_fill(past[:, :, None], 0)
+
+    @torch.no_grad()
+    def score_variants(self, ref_ids, positions, alts, groups=None, horizon=64, vocab_size=None, max_window_tokens=None):
+        """Zero-shot effect of M single-base substitutions: ``ref_ids`` (G, L), ``positions`` (M,) with 1 <= positions[m] <= L - 1,
+        ``alts`` (M,) the substituted token -> ``VariantScores(site, downstream, llr, complete)``, log-likelihood differences (alt - ref)
+        under the model, with lsm = log_softmax over the first ``vocab_size`` logit columns (None: all), g = groups[m], p = positions[m],
+        T = ``horizon``:
+
+            site[m]          = lsm(ref_logits[g, p - 1])[alt] - lsm(ref_logits[g, p - 1])[ref[p]]
+            downstream[m, i] = lsm(logits[m, i])[ref[p + i + 1]] - lsm(ref_logits[g, p + i])[ref[p + i + 1]]     for p + i + 1 <= L - 1, else 0
+            llr[m]           = site[m] + downstream[m].sum()
+            complete[m]      = p + T >= L - 1
+
+        ``logits`` are ``forward_edited_windows``' over the window tokens ``[alt, ref[p + 1], ..., ref[p + T - 1]]``.  Where ``complete`` holds,
+        ``llr`` is the log-likelihood ratio of the whole sequences; elsewhere it is TRUNCATED at the horizon: the terms of positions past
+        p + T are left out (they decay with the filter but are not zero).  1 <= horizon <= 1024."""
+        T = int(horizon)
+        G, L, M, groups = self._check_edit_windows(ref_ids, positions, groups, T, what="horizon")
+        if not torch.is_tensor(alts) or alts.shape != (M,) or alts.dtype != torch.int64 or alts.device != ref_ids.device:
+            raise ValueError(f"alts has to be an ({M},) int64 tensor on {ref_ids.device}")
+        Vall = self.lm_head.weight.shape[0]
+        V = Vall if vocab_size is None else int(vocab_size)
+        if not 1 <= V <= Vall:
+            raise ValueError(f"vocab_size={vocab_size}: the model has {Vall} logit columns")
+        if int(positions.min()) < 1:
+            raise ValueError(f"positions hold entries outside [1, {L - 1}]: a substitution at position 0 has no context to be scored from")
+        if int(alts.min()) < 0 or int(alts.max()) >= V:
+            raise ValueError(f"alts hold token ids outside [0, {V})")
+        if int(ref_ids.min()) < 0 or int(ref_ids.max()) >= V:
+            raise ValueError(f"ref_ids hold token ids outside [0, {V})")
+        dev = ref_ids.device
+        idx = positions[:, None] + torch.arange(T + 1, device=dev)[None, :]                       # (M, T + 1): p ... p + T
+        ref_tok = ref_ids[groups[:, None], idx.clamp(max=L - 1)]                                  # ref[p + j], clipped past the end
+        window = torch.cat([alts[:, None], ref_tok[:, 1:T]], dim=1)
+        ref_logits, logits = self.forward_edited_windows(ref_ids, positions, window, groups=groups, max_window_tokens=max_window_tokens)
+        # the reference's rows p - 1 ... p + T - 1, gathered before the softmax: M (T + 1) rows, not G L
+        rows = ref_logits[groups[:, None], (idx - 1).clamp(max=L - 1)][..., :V].float()           # (M, T + 1, V)
+        lsm_ref = torch.log_softmax(rows, dim=-1)
+        lsm_alt = torch.log_softmax(logits[..., :V].float(), dim=-1)                              # (M, T, V)
+        site = (lsm_ref[:, 0].gather(-1, alts[:, None]) - lsm_ref[:, 0].gather(-1, ref_tok[:, :1])).squeeze(-1)
+        nxt = ref_tok[:, 1:, None]                                                                # ref[p + i + 1], i < T
+        down = (lsm_alt.gather(-1, nxt) - lsm_ref[:, 1:].gather(-1, nxt)).squeeze(-1)
+        down = down.masked_fill(idx[:, 1:] > L - 1, 0)
+        VariantScores = namedtuple("VariantScores", ["site", "downstream", "llr", "complete"])
+        return VariantScores(site=site, downstream=down, llr=site + down.sum(-1), complete=positions + T >= L - 1)
+
+    @torch.no_grad()
+    def saturation_mutagenesis(self, ref_ids, start, stop, alphabet=(7, 8, 9, 10), horizon=64, vocab_size=None, max_window_tokens=None):
+        """``score_variants``' ``llr`` of every substitution of ``alphabet`` at every position of ``[start, stop)`` of ONE reference
+        ``ref_ids`` (L,) -> (stop - start, len(alphabet)) fp32; the reference base's own entry is exactly 0.  1 <= start < stop <= L.
+        One ``score_variants`` call over (stop - start) len(alphabet) variants (position-major), so its other entries are that call's."""
+        if not torch.is_tensor(ref_ids) or ref_ids.dim() != 1 or ref_ids.dtype != torch.int64:
+            raise ValueError("ref_ids has to be an (L,) int64 tensor: saturation_mutagenesis takes one reference")
+        L = ref_ids.shape[0]
+        start, stop = int(start), int(stop)
+        if not 1 <= start < stop <= L:
+            raise ValueError(f"start={start}, stop={stop}: positions 1 <= start < stop <= {L}")
+        alphabet = [int(a) for a in alphabet]
+        if len(alphabet) < 1:
+            raise ValueError("alphabet holds no token")
+        A = len(alphabet)
+        pos = torch.arange(start, stop, device=ref_ids.device).repeat_interleave(A)
+        alts = torch.tensor(alphabet, dtype=torch.int64, device=ref_ids.device).repeat(stop - start)
+        llr = self.score_variants(ref_ids[None], pos, alts, horizon=horizon, vocab_size=vocab_size, max_window_tokens=max_window_tokens).llr
+        return llr.masked_fill(alts == ref_ids[pos], 0).view(stop - start, A)
+
     def loss(self, input_ids, targets, ignore_index=-100):
         """next-token cross entropy (src/tasks/metrics.py cross_entropy over the flattened logits), logits in fp32"""
         logits = self.forward(input_ids)[0].logits
